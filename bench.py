@@ -7,6 +7,9 @@ GPUs -> 16 seqs/GPU weak scaling, gen len fixed 512, top_p 0.9 / top_k
 1000, 4 PPO minibatches), synthetic prompts, random-init weights, bf16.
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+          [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times K steps and prints one JSON result
+line; anything else the benchmark may measure belongs behind --full.
 Multi-GPU (driver):  python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 One process per GPU over RCCL; per-model data parallelism (weak scaling:
@@ -24,19 +27,31 @@ _TUNED = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                       "realhf_amd", "data", "tunableop_gfx950.csv")
 if os.path.exists(_TUNED) and "PYTORCH_TUNABLEOP_ENABLED" not in os.environ:
     # TunableOp appends the device ordinal before .csv on read — stage a
-    # copy per possible ordinal under /tmp.  All torchrun ranks execute
-    # this concurrently: copy to a rank-unique temp then os.replace (atomic
-    # on POSIX) so no rank ever reads a half-written CSV.
+    # copy per possible ordinal in a per-user temp directory (a fixed name
+    # shared by all users cannot be replaced by the second user to run).
+    # All torchrun ranks execute this concurrently: copy to a rank-unique
+    # temp then os.replace (atomic on POSIX) so no rank ever reads a
+    # half-written CSV.
     import shutil as _sh
+    import tempfile as _tf
 
+    _stage = os.path.join(_tf.gettempdir(), f"realhf_amd_{os.getuid()}")
+    os.makedirs(_stage, mode=0o700, exist_ok=True)
     _pid = os.getpid()
     for _d in range(8):
-        _tmp = f"/tmp/realhf_tunableop{_d}.csv.{_pid}"
+        _tmp = os.path.join(_stage, f"tunableop{_d}.csv.{_pid}")
         _sh.copy(_TUNED, _tmp)
-        os.replace(_tmp, f"/tmp/realhf_tunableop{_d}.csv")
+        os.replace(_tmp, os.path.join(_stage, f"tunableop{_d}.csv"))
     os.environ["PYTORCH_TUNABLEOP_ENABLED"] = "1"
     os.environ["PYTORCH_TUNABLEOP_TUNING"] = "0"
-    os.environ["PYTORCH_TUNABLEOP_FILENAME"] = "/tmp/realhf_tunableop.csv"
+    os.environ["PYTORCH_TUNABLEOP_FILENAME"] = os.path.join(
+        _stage, "tunableop.csv")
+
+# sum dQ of the attention backward in a fixed order, so that two runs with
+# the same arguments compute the same step bit for bit (--dump-outputs).
+# A/B, 6 timed steps, two runs each: 4395-4409 ms/step with it, 4388-4395
+# with atomics (REALHF_AMD_ATTN_BWD_DET=0) -- inside the run-to-run spread
+os.environ.setdefault("REALHF_AMD_ATTN_BWD_DET", "1")
 
 import numpy as np
 import torch
@@ -46,6 +61,66 @@ import torch.distributed as dist
 def log(msg):
     r = int(os.environ.get("RANK", "0"))
     print(f"[bench rank{r}] {msg}", flush=True, file=__import__("sys").stderr)
+
+
+# --dump-outputs: elements kept per array (larger arrays are sampled) and
+# the hard cap on everything written
+_DUMP_MAX_ELEMS = 2 * 2**20
+_DUMP_MAX_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, sample, astats, cstats, params, first):
+    """Write what the last timed step returned as out_dir/<name>.npy.
+
+    rollout_<key>: every tensor of the step's rollout batch (generated
+    sequences, logprobs, masks, rewards, ref logprobs, values);
+    actor_stats / critic_stats: the train_step stat dicts as float64
+    vectors in sorted-key order (names in manifest.json);
+    <role>_params: the updated flat parameters;
+    first_rollout_<key>: the rollout batch of the very first step executed
+    (warmup included), i.e. computed from the initial weights alone.
+    Arrays are float32 in their own shape; one larger than
+    _DUMP_MAX_ELEMS is flattened and reduced to a fixed sample whose
+    indices are seeded by the array's name, so two runs pick the same
+    elements.
+    """
+    import zlib
+
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = {}
+    total = 0
+
+    def save(name, arr, **extra):
+        nonlocal total
+        total += arr.nbytes
+        assert total <= _DUMP_MAX_BYTES, (name, total)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        manifest[name] = dict(shape=list(arr.shape), dtype=str(arr.dtype),
+                              **extra)
+
+    def save_tensor(name, t):
+        t = t.detach()
+        extra = {}
+        if t.numel() > _DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (_DUMP_MAX_ELEMS,), generator=g)
+            extra = dict(sampled_from=list(t.shape), sample_seed=g.initial_seed())
+            t = t.reshape(-1)[idx.to(t.device)]
+        save(name, t.to(torch.float32).cpu().numpy(), **extra)
+
+    for k in sorted(sample.keys):
+        save_tensor("rollout_" + k, sample.data[k])
+    for name, stats in (("actor_stats", astats), ("critic_stats", cstats)):
+        keys = sorted(stats)
+        save(name, np.array([float(stats[k]) for k in keys], dtype=np.float64),
+             keys=keys)
+    for role, flat in params.items():
+        save_tensor(role + "_params", flat)
+    for k in sorted(first):
+        save_tensor("first_rollout_" + k, first[k])
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    log(f"dumped {len(manifest)} arrays ({total / 2**20:.1f} MiB) to {out_dir}")
 
 
 def main():
@@ -72,7 +147,19 @@ def main():
                         "traffic was 15%% of GPU time in rocprof) — "
                         "offload pays only when memory forces it (70B "
                         "tier, or --offload-set ref,rew)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned (rollout tensors, train stats, a "
+                        "seeded sample of the updated actor/critic "
+                        "parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check "
+                        "that needs runs of its own.  The benchmark has "
+                        "none today; a plain run does only setup, warmup, "
+                        "the timed steps and the result line")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -272,7 +359,7 @@ def main():
         with scope("critic"):
             cstats = critic_iface.train_step(models["critic"], sample)
         t = mark("critic_train", t)
-        return astats, cstats
+        return astats, cstats, sample
 
     for n in frozen:
         models[n].module.model.async_offload()
@@ -284,8 +371,19 @@ def main():
             torch.cuda.synchronize()
 
     log(f"warmup x{args.warmup}...")
+    # --dump-outputs keeps the rollout batch of the first executed step
+    # (copied: it is computed from the initial weights alone) and a
+    # reference to the last one; a plain run keeps neither
+    first_rollout = rollout = None
+
+    def copy_rollout(sample):
+        return {k: sample.data[k].detach().clone() for k in sample.keys}
+
     for i in range(args.warmup):
-        ppo_step()
+        rollout = ppo_step()[2]
+        if args.dump_outputs and first_rollout is None:
+            first_rollout = copy_rollout(rollout)
+        rollout = None
         m2 = torch.cuda.max_memory_allocated() / 2**30 if use_cuda else 0.0
         log(f"warmup step {i} done; peak mem={m2:.1f} GiB")
     barrier_sync()
@@ -293,7 +391,11 @@ def main():
     phase_t.clear()
     t0 = time.time()
     for i in range(args.steps):
-        astats, cstats = ppo_step()
+        astats, cstats, rollout = ppo_step()
+        if not args.dump_outputs:
+            rollout = None
+        elif first_rollout is None:  # --warmup 0: no earlier place for it
+            first_rollout = copy_rollout(rollout)
         log(f"step {i}: actor_loss={astats.get('actor_loss', 0):.4f} "
             f"kl={astats.get('kl', 0):.4f}")
     barrier_sync()
@@ -323,6 +425,14 @@ def main():
                 dist.all_reduce(hi, op=dist.ReduceOp.MAX)
                 assert torch.allclose(lo, hi, rtol=1e-6, atol=0), (
                     f"{n}: DP replicas diverged after training ({lo} vs {hi})")
+
+    if args.dump_outputs and rank == 0:
+        with torch.no_grad():
+            dump_outputs(
+                args.dump_outputs, rollout, astats, cstats,
+                {n: models[n].module.module.flat_param
+                 for n in ("actor", "critic")},
+                first_rollout)
 
     n_gpus = world
     total_samples = args.seqs_per_gpu * n_gpus * args.steps

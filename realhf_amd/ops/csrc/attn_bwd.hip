@@ -13,8 +13,11 @@
 //   dP^T = V dO^T             (A = V row frag, B = dO row frag)
 //   dS^T = P^T o (dP^T - D[q]) * scale
 //   dK += dS^T Q              (A = dS^T via LDS, B = Q via tr16)
-//   dQ += dS K  -> fp32 atomics (A = dS via tr16 of the shared dS^T
-//                 tile, B = K via tr16; hd chunks split across waves)
+//   dQ += dS K  -> fp32 atomics, or (opt-in: max_seqlen given and the
+//                 partials fit) per-kv-block fp32 partials summed in
+//                 block order by bw_reduce_dq, bit-reproducible (A = dS
+//                 via tr16 of the shared dS^T tile, B = K via tr16; hd
+//                 chunks split across waves)
 // dK/dV are written per Q-HEAD to fp32 buffers (no atomics); the host
 // sums GQA groups.  D = rowsum(dO*O) and the final casts happen in
 // torch (fp32).
@@ -62,6 +65,7 @@ DEVINL int bw_blk_lookup(const int* __restrict__ off, int bs, int blk_id) {
 #define BW_QT 32      // queries per tile
 #define BW_PAD 8
 #define BW_TPAD 16    // pad for tr16-read tiles (bank spread, fwd-proven)
+#define BW_DET_MAX_BYTES (2L << 30)  // cap on the deterministic-dQ partials
 
 DEVINL bf16x8 tr16_bfrag(const __bf16* base, int pitch, int krow0, int col4) {
   // two transpose reads -> one 8-deep fragment (k = rows, n = cols)
@@ -75,7 +79,56 @@ DEVINL bf16x8 tr16_bfrag(const __bf16* base, int pitch, int krow0, int col4) {
   return vb;
 }
 
+// Query rows [*qb, *up) of a sequence of length L receive a dQ
+// contribution from the kv block starting at key k0 (the q-tile loop of
+// attn_varlen_bwd_kernel); false when the block visits no q tile.
+DEVINL bool bw_q_range(int k0, int L, bool causal, int window,
+                       int* qb, int* up) {
+  const int q_begin = causal ? (k0 / BW_QT) * BW_QT : 0;
+  const int q_end = (window > 0) ? min(L, k0 + BW_KV + window - 1) : L;
+  if (q_end <= q_begin) return false;
+  *qb = q_begin;
+  *up = q_begin + ((q_end - q_begin + BW_QT - 1) / BW_QT) * BW_QT;
+  return true;
+}
+
+// Deterministic dQ: dq[row] = sum over the kv blocks that visited the row,
+// in ascending block order, of the per-block partials dq_part[slot][...].
+// One thread per 4 floats of [total, nq, HD]; only visited (slot, row)
+// cells are read, so dq_part needs no zero fill.  nslot comes from the
+// caller's max_seqlen; it decides only which blocks are summed in order,
+// never whether a contribution is counted.
 template <int HD>
+__global__ void bw_reduce_dq(const float* __restrict__ part,
+                             float* dq,
+                             const int* __restrict__ cu, int bs, int total,
+                             int nq, int nslot, bool causal, int window) {
+  const long n4 = (long)total * nq * (HD / 4);
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n4) return;
+  const int row = (int)(idx / ((long)nq * (HD / 4)));
+  int lo = 0, hi = bs;  // largest i with cu[i] <= row
+  while (lo + 1 < hi) {
+    int mid = (lo + hi) >> 1;
+    if (cu[mid] <= row) lo = mid; else hi = mid;
+  }
+  const int s0 = cu[lo], L = cu[lo + 1] - s0, lr = row - s0;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (lr >= 0 && lr < L) {
+    const int nblk = min((L + BW_KV - 1) / BW_KV, nslot);
+    for (int b = 0; b < nblk; b++) {
+      int qb, up;
+      if (!bw_q_range(b * BW_KV, L, causal, window, &qb, &up)) continue;
+      if (lr < qb || lr >= up) continue;
+      acc += ((const f32x4*)part)[(long)b * n4 + idx];
+    }
+  }
+  // dq arrives zero-filled except for blocks beyond the last slot (a
+  // sequence longer than max_seqlen), which added into it atomically
+  ((f32x4*)dq)[idx] = acc + ((const f32x4*)dq)[idx];
+}
+
+template <int HD, bool DET>
 __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
@@ -83,7 +136,8 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
     const int* __restrict__ cu_seqlens, const int* __restrict__ blk_offsets,
     int n_seqs, float* __restrict__ dq32,
     float* __restrict__ dk32, float* __restrict__ dv32,
-    int nq, int nkv, float scale, bool causal, int window) {
+    int nq, int nkv, float scale, bool causal, int window,
+    float* __restrict__ dq_part, int nslot, long part_stride) {
   constexpr int HDCH = HD / 32;
   const int blk = blockIdx.x;
   if (blk >= blk_offsets[n_seqs]) return;  // over-provisioned grid tail
@@ -213,7 +267,8 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
       }
     }
 
-    // ---- dQ += dS K (cooperative over hd chunks; fp32 atomics) -----
+    // ---- dQ += dS K (cooperative over hd chunks; DET: plain stores
+    // into this kv block's slot, else fp32 atomics) -------------------
     // A = dS[q][key] via tr16 of ds_all (k = LDS row = key, i = col = q,
     // one 16-q column window per qs2); B = K[key][hd] via tr16 of k_s.
     {
@@ -236,9 +291,20 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
           #pragma unroll
           for (int r = 0; r < 4; r++) {
             const int qrow = q0 + qs2 * 16 + g * 4 + r;
-            if (qrow < L)
-              atomicAdd(&dq32[((long)(s0 + qrow) * nq + qh) * HD + t * 16 + i16],
-                        dq_acc[r]);
+            if (qrow >= L) continue;
+            const long o = ((long)(s0 + qrow) * nq + qh) * HD + t * 16 + i16;
+            if (DET) {
+              // plain store into this kv block's slot (slot = block index
+              // within the sequence); bw_reduce_dq sums slots in order
+              const int slot = k0 / BW_KV;
+              if (slot < nslot)
+                dq_part[(long)slot * part_stride + o] = dq_acc[r];
+              else  // sequence longer than max_seqlen promised: stay
+                    // correct (no slot to write), only the order is lost
+                atomicAdd(&dq32[o], dq_acc[r]);
+            } else {
+              atomicAdd(&dq32[o], dq_acc[r]);
+            }
           }
         }
       }
@@ -264,7 +330,7 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
 std::vector<torch::Tensor> attn_varlen_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
     torch::Tensor lse, torch::Tensor Dsum, torch::Tensor cu_seqlens,
-    bool causal, double scale, long window) {
+    bool causal, double scale, long window, long max_seqlen) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous() &&
               dout.is_contiguous());
@@ -277,29 +343,53 @@ std::vector<torch::Tensor> attn_varlen_bwd(
   hipLaunchKernelGGL(bw_build_blk_offsets, dim3(1), dim3(64), 0,
     cur_stream(), cu_dev.data_ptr<int>(), bs, BW_KV, blk_off.data_ptr<int>());
   auto f32 = q.options().dtype(torch::kFloat);
+  // Deterministic dQ needs one [total, nq, hd] fp32 slot per kv block of
+  // the longest sequence.  It is opt-in: max_seqlen = 0 (the default)
+  // keeps the atomic path and allocates nothing extra.  When the slots
+  // would exceed BW_DET_MAX_BYTES (long-context batches) the call also
+  // uses atomics, whose summation order varies from run to run.
+  const long part_stride = (long)total * nq * hd;
+  const long nslot = max_seqlen > 0 ? (max_seqlen + BW_KV - 1) / BW_KV : 0;
+  const bool det = nslot > 0 && total > 0 &&
+                   nslot * part_stride * 4 <= BW_DET_MAX_BYTES;
   auto dq32 = torch::zeros({(long)total, (long)nq, (long)hd}, f32);
+  torch::Tensor dq_part;
+  if (det) dq_part = torch::empty({nslot, (long)total, (long)nq, (long)hd}, f32);
+  float* part_ptr = det ? dq_part.data_ptr<float>() : nullptr;
   auto dk32 = torch::empty({(long)total, (long)nq, (long)hd}, f32);
   auto dv32 = torch::empty({(long)total, (long)nq, (long)hd}, f32);
   dim3 grid((unsigned)(total / BW_KV + bs), nq);
   TORCH_CHECK(hd == 128 || hd == 64, "attn_varlen_bwd: hd 64/128 only");
+#define BW_LAUNCH(HD_, DET_)                                              \
+  hipLaunchKernelGGL((attn_varlen_bwd_kernel<HD_, DET_>), grid,           \
+    dim3(64 * BW_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
+    (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),                 \
+    (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),                  \
+    Dsum.data_ptr<float>(), cu_dev.data_ptr<int>(),                       \
+    blk_off.data_ptr<int>(), bs,                                          \
+    dq32.data_ptr<float>(), dk32.data_ptr<float>(), dv32.data_ptr<float>(), \
+    nq, nkv, (float)scale, causal, (int)window,                           \
+    part_ptr, (int)nslot, part_stride)
   if (hd == 128) {
-    hipLaunchKernelGGL((attn_varlen_bwd_kernel<128>), grid,
-      dim3(64 * BW_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),
-      (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
-      (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),
-      Dsum.data_ptr<float>(), cu_dev.data_ptr<int>(),
-      blk_off.data_ptr<int>(), bs,
-      dq32.data_ptr<float>(), dk32.data_ptr<float>(), dv32.data_ptr<float>(),
-      nq, nkv, (float)scale, causal, (int)window);
+    if (det) BW_LAUNCH(128, true); else BW_LAUNCH(128, false);
   } else {
-    hipLaunchKernelGGL((attn_varlen_bwd_kernel<64>), grid,
-      dim3(64 * BW_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),
-      (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
-      (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),
-      Dsum.data_ptr<float>(), cu_dev.data_ptr<int>(),
-      blk_off.data_ptr<int>(), bs,
-      dq32.data_ptr<float>(), dk32.data_ptr<float>(), dv32.data_ptr<float>(),
-      nq, nkv, (float)scale, causal, (int)window);
+    if (det) BW_LAUNCH(64, true); else BW_LAUNCH(64, false);
+  }
+#undef BW_LAUNCH
+  if (det) {
+    const long n4 = part_stride / 4;
+    dim3 rgrid((unsigned)((n4 + 255) / 256));
+    if (hd == 128) {
+      hipLaunchKernelGGL((bw_reduce_dq<128>), rgrid, dim3(256), 0,
+        cur_stream(), part_ptr, dq32.data_ptr<float>(),
+        cu_dev.data_ptr<int>(), bs, total, nq, (int)nslot, causal,
+        (int)window);
+    } else {
+      hipLaunchKernelGGL((bw_reduce_dq<64>), rgrid, dim3(256), 0,
+        cur_stream(), part_ptr, dq32.data_ptr<float>(),
+        cu_dev.data_ptr<int>(), bs, total, nq, (int)nslot, causal,
+        (int)window);
+    }
   }
   CHECK_CUDA_OK();
   return {dq32, dk32, dv32};

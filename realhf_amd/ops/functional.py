@@ -314,6 +314,10 @@ class _AttnVarlenFn(torch.autograd.Function):
         if os.environ.get("REALHF_AMD_NO_HIP_ATTN_BWD") != "1":
             # hand-written MFMA backward (attn_bwd.hip): kv-stationary,
             # dQ via fp32 atomics, per-q-head dK/dV reduced here for GQA;
+            # REALHF_AMD_ATTN_BWD_DET=1 (opt-in; bench.py sets it) sums dQ
+            # from per-kv-block partials in block order instead, which is
+            # bit-reproducible but allocates ceil(max_seqlen/64) dQ-sized
+            # fp32 slots per call;
             # sliding-window via key-range restriction like the forward.
             # In-context A/B: 3.51 vs 3.19 samples/s over the padded
             # recompute fallback (REALHF_AMD_NO_HIP_ATTN_BWD=1).
@@ -323,6 +327,8 @@ class _AttnVarlenFn(torch.autograd.Function):
             dq32, dk32, dv32 = C.attn_varlen_bwd(
                 q, k, v, dout, lse, dsum, cu_seqlens, ctx.causal, ctx.scale,
                 int(ctx.window or 0),
+                int(ctx.max_seqlen)
+                if os.environ.get("REALHF_AMD_ATTN_BWD_DET") == "1" else 0,
             )
             nq, nkv = q.shape[1], k.shape[1]
             rep = nq // nkv

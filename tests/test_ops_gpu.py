@@ -602,6 +602,64 @@ def test_attn_varlen_bwd_sliding_window():
         assert not torch.allclose(dq32, dq_f)
 
 
+@pytest.mark.parametrize("nq,nkv,hd,window,causal,lens", [
+    (8, 8, 128, 0, True, [96, 64, 130, 32]),    # several kv blocks, ragged
+    (8, 2, 128, 100, True, [96, 64, 200, 40]),  # GQA + binding window
+    (4, 4, 64, 0, True, [1, 63, 65, 129, 31]),  # hd 64, lengths at the tiles
+    (8, 8, 128, 0, False, [96, 64, 130, 32]),   # non-causal: every block
+])                                              # visits every query tile
+def test_attn_varlen_bwd_dq_deterministic(nq, nkv, hd, window, causal, lens):
+    """With max_seqlen the backward sums dQ from per-kv-block partials in
+    a fixed order: bit-identical from call to call, and equal to the
+    atomic path (the same fp32 partials, summed in another order) up to
+    fp32 reassociation of at most ceil(max_len/64) <= 4 terms of
+    magnitude <~ 1, i.e. a few 2^-24 — bound 1e-5.  A max_seqlen smaller
+    than the longest sequence may cost the fixed order, never a
+    contribution."""
+    from realhf_amd.ops import functional as F
+
+    torch.manual_seed(29)
+    total = sum(lens)
+    cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)),
+                      dtype=torch.int32, device="cuda")
+    q = (torch.randn(total, nq, hd, device="cuda") * 0.3).to(torch.bfloat16)
+    k = (torch.randn(total, nkv, hd, device="cuda") * 0.3).to(torch.bfloat16)
+    v = (torch.randn(total, nkv, hd, device="cuda") * 0.3).to(torch.bfloat16)
+    dout = (torch.randn(total, nq, hd, device="cuda") * 0.3).to(torch.bfloat16)
+    scale = hd ** -0.5
+
+    qr = q.float().requires_grad_(True)
+    kr = k.float().requires_grad_(True)
+    vr = v.float().requires_grad_(True)
+    ref = F._attn_varlen_blocked_torch(qr, kr, vr, cu, causal, scale,
+                                       window=window or None)
+    ref_dq, _, _ = torch.autograd.grad(ref, (qr, kr, vr), dout.float())
+
+    out, lse = C.attn_varlen_fwd(q, k, v, cu, max(lens), causal, scale, window)
+    dsum = (dout.float() * out.float()).sum(-1)
+    args = (q, k, v, dout, lse, dsum, cu, causal, scale, window)
+    dq_a, dk_a, dv_a = C.attn_varlen_bwd(*args)  # atomics
+    # The partial buffer is not zero-filled, so a read of a cell that no
+    # block wrote must show.  The buffer is allocated inside the op; free
+    # a NaN-filled block of exactly its shape just before, which the
+    # caching allocator hands back for the next same-sized request (best
+    # effort: the comparisons below do not depend on it).
+    nslot = (max(lens) + 63) // 64
+    junk = torch.full((nslot, total, nq, hd), float("nan"), device="cuda")
+    del junk
+    dq_1, dk_1, dv_1 = C.attn_varlen_bwd(*args, max(lens))
+    dq_2, _, _ = C.attn_varlen_bwd(*args, max(lens))
+    assert torch.isfinite(dq_1).all()
+    assert torch.equal(dq_1, dq_2)
+    assert torch.equal(dk_1, dk_a) and torch.equal(dv_1, dv_a)
+    torch.testing.assert_close(dq_1, dq_a, atol=1e-5, rtol=1e-5)
+    torch.testing.assert_close(dq_1, ref_dq, atol=0.15, rtol=5e-2)
+    # understated max_seqlen: one slot, the later blocks have none
+    assert max(lens) > 64
+    dq_u, _, _ = C.attn_varlen_bwd(*args, 64)
+    torch.testing.assert_close(dq_u, dq_a, atol=1e-5, rtol=1e-5)
+
+
 def test_offloaded_adamw_matches_resident():
     """Pipelined host-offloaded AdamW (chunked H2D/compute/D2H on a side
     stream) must produce the same parameters as the GPU-resident
