@@ -10,8 +10,8 @@ all experts and stubs the expert group to self (megatron.py:108, SURVEY.md
 with token all-to-all over xGMI; EP degree = cfg.moe.expert_parallel_size.
 
 Expert GEMMs run through the hand-written MFMA grouped-GEMM kernels for
-BOTH inference and training (fwd: ops/csrc/grouped_gemm.hip; bwd dX/dW:
-ops/csrc/grouped_gemm_bwd.hip, via the _GroupedGemm autograd function) —
+BOTH inference and training (fwd and bwd dX/dW: ops/csrc/grouped_gemm.hip,
+via the _GroupedGemm autograd function) —
 matching the reference's grouped_gemm.ops.gmm training path
 (experts.py:194-207).  The per-expert rocBLAS loop remains as the
 CPU/odd-shape fallback (REALHF_AMD_MOE_LOOP=1 forces it, for tests).
@@ -261,7 +261,7 @@ class MoELayer(torch.nn.Module):
         """x_sorted: tokens grouped by local expert; counts_cpu [n_local].
 
         Training AND inference run through the hand-written MFMA grouped
-        GEMM (fwd: grouped_gemm.hip, bwd dX/dW: grouped_gemm_bwd.hip) —
+        GEMM (fwd and bwd dX/dW: grouped_gemm.hip) —
         the reference trains through grouped_gemm.ops.gmm
         (experts.py:194-207); the per-expert rocBLAS loop below is only
         the CPU/odd-shape fallback."""

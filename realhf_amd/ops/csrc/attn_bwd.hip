@@ -22,43 +22,9 @@
 // sums GQA groups.  D = rowsum(dO*O) and the final casts happen in
 // torch (fp32).
 //
-// MFMA lane maps as in attn_varlen.hip (verified by mfma_probe):
-//   A[i][k]: i = lane&15, k = (lane>>4)*8 + j
-//   B[k][n]: n = lane&15, k = (lane>>4)*8 + j
-//   C[i][n]: n = lane&15, i = (lane>>4)*4 + r
-// tr16 hardware-transpose read (verified by tr16_probe): reading the
-// 8-byte chunk at src[kbase + g*8 + (i16>>2) (+4)][nbase + (i16&3)*4]
-// yields the B (or A — identical lane geometry) fragment with k = LDS
-// row, n(or i) = LDS column.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4v;
-typedef __attribute__((address_space(3))) bf16x4v lds_b64_t;
-
-static __global__ void bw_build_blk_offsets(const int* __restrict__ cu,
-                                             int bs, int blk,
-                                             int* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    int acc = 0;
-    for (int i = 0; i < bs; i++) {
-      out[i] = acc;
-      int L = cu[i + 1] - cu[i];
-      acc += (L + blk - 1) / blk;
-    }
-    out[bs] = acc;
-  }
-}
-
-DEVINL int bw_blk_lookup(const int* __restrict__ off, int bs, int blk_id) {
-  int lo = 0, hi = bs;  // largest i with off[i] <= blk_id
-  while (lo + 1 < hi) {
-    int mid = (lo + hi) >> 1;
-    if (off[mid] <= blk_id) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// MFMA lane maps, the tr16 hardware-transpose fragment read and the block
+// mapping are in mfma.h (verified by mfma_probe / tr16_probe).
+#include "mfma.h"
 
 #define BW_WAVES 4
 #define BW_KV 64      // keys per workgroup (16 per wave)
@@ -66,18 +32,6 @@ DEVINL int bw_blk_lookup(const int* __restrict__ off, int bs, int blk_id) {
 #define BW_PAD 8
 #define BW_TPAD 16    // pad for tr16-read tiles (bank spread, fwd-proven)
 #define BW_DET_MAX_BYTES (2L << 30)  // cap on the deterministic-dQ partials
-
-DEVINL bf16x8 tr16_bfrag(const __bf16* base, int pitch, int krow0, int col4) {
-  // two transpose reads -> one 8-deep fragment (k = rows, n = cols)
-  bf16x4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_b64_t*)(base + (long)krow0 * pitch + col4));
-  bf16x4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_b64_t*)(base + (long)(krow0 + 4) * pitch + col4));
-  bf16x8 vb;
-  #pragma unroll
-  for (int j = 0; j < 4; j++) { vb[j] = r0[j]; vb[4 + j] = r1[j]; }
-  return vb;
-}
 
 // Query rows [*qb, *up) of a sequence of length L receive a dQ
 // contribution from the kv block starting at key k0 (the q-tile loop of
@@ -143,14 +97,11 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
   if (blk >= blk_offsets[n_seqs]) return;  // over-provisioned grid tail
   const int qh = blockIdx.y;
   const int kvh = qh / (nq / nkv);
-  const int seq = bw_blk_lookup(blk_offsets, n_seqs, blk);
+  const int seq = blk_lookup(blk_offsets, n_seqs, blk);
   const int k0 = (blk - blk_offsets[seq]) * BW_KV;
   const int s0 = cu_seqlens[seq], s1 = cu_seqlens[seq + 1];
   const int L = s1 - s0;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int i16 = lane & 15;
-  const int g = lane >> 4;
+  const auto [lane, w, i16, g] = mfma_lane();
 
   __shared__ __bf16 k_s[BW_KV][HD + BW_TPAD];   // row-major; tr16-read too
   __shared__ __bf16 v_s[BW_KV][HD + BW_PAD];
@@ -227,8 +178,8 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
       for (int c = 0; c < HDCH; c++) {
         bf16x8 qb = *(const bf16x8*)(&q_s[qs * 16 + i16][c * 32 + g * 8]);
         bf16x8 db = *(const bf16x8*)(&do_s[qs * 16 + i16][c * 32 + g * 8]);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag[c], qb, a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag[c], db, a2, 0, 0, 0);
+        a1 = mfma16(kfrag[c], qb, a1);
+        a2 = mfma16(vfrag[c], db, a2);
       }
       st[qs] = a1;
       dpt[qs] = a2;
@@ -262,8 +213,8 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
       for (int t = 0; t < HD / 16; t++) {
         bf16x8 dob = tr16_bfrag(&do_s[0][0], HD + BW_TPAD, krow0, t * 16 + col4);
         bf16x8 qb = tr16_bfrag(&q_s[0][0], HD + BW_TPAD, krow0, t * 16 + col4);
-        dv_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, dob, dv_acc[t], 0, 0, 0);
-        dk_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, qb, dk_acc[t], 0, 0, 0);
+        dv_acc[t] = mfma16(pa, dob, dv_acc[t]);
+        dk_acc[t] = mfma16(da, qb, dk_acc[t]);
       }
     }
 
@@ -286,7 +237,7 @@ __global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
                                     qs2 * 16 + col4);
             bf16x8 kb = tr16_bfrag(&k_s[0][0], HD + BW_TPAD, krow0,
                                    t * 16 + col4);
-            dq_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa, kb, dq_acc, 0, 0, 0);
+            dq_acc = mfma16(dsa, kb, dq_acc);
           }
           #pragma unroll
           for (int r = 0; r < 4; r++) {
@@ -338,10 +289,7 @@ std::vector<torch::Tensor> attn_varlen_bwd(
   int nkv = k.size(1);
   auto cu_dev = cu_seqlens.to(torch::kInt).to(q.device());
   int bs = cu_dev.numel() - 1;
-  auto iopts = torch::TensorOptions().dtype(torch::kInt).device(q.device());
-  auto blk_off = torch::empty({(long)bs + 1}, iopts);
-  hipLaunchKernelGGL(bw_build_blk_offsets, dim3(1), dim3(64), 0,
-    cur_stream(), cu_dev.data_ptr<int>(), bs, BW_KV, blk_off.data_ptr<int>());
+  auto blk_off = build_blk_offsets<BW_KV>(cu_dev);
   auto f32 = q.options().dtype(torch::kFloat);
   // Deterministic dQ needs one [total, nq, hd] fp32 slot per kv block of
   // the longest sequence.  It is opt-in: max_seqlen = 0 (the default)

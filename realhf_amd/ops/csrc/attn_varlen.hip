@@ -5,21 +5,17 @@
 // Structure (correctness-first instance of the guide's §B prefill recipe):
 //   grid = (q_block, q_head); workgroup = 512 threads = 8 waves.
 //   Each workgroup owns 128 query rows of one sequence+head (wave w: 16
-//   rows) so the cooperative K/V staging amortizes over 2x the MFMA work.  KV tiles of 64 keys are staged cooperatively in LDS — K
-//   row-major [64][136] (8-elem pad), V TRANSPOSED [128][72] so the PV
-//   B-fragment is a contiguous ds_read_b128.  Online softmax state (m, l)
-//   is held per C-row in registers, reduced with shfl_xor over the 16-lane
+//   rows) so the cooperative K/V staging amortizes over 2x the MFMA work.
+//   KV tiles of 64 keys are staged cooperatively in LDS — K row-major
+//   [64][136] (8-elem pad), V row-major [64][144], read by the PV stage
+//   through the tr16 hardware transpose.  Online softmax state (m, l) is
+//   held per C-row in registers, reduced with shfl_xor over the 16-lane
 //   column groups.
 //
-// MFMA: v_mfma_f32_16x16x32_bf16.  Lane maps (guide §3):
-//   A[i][k]:  i = lane&15, k = (lane>>4)*8 + j   (j = 0..7, 4 VGPRs bf16)
-//   B[k][n]:  n = lane&15, k = (lane>>4)*8 + j
-//   C/D[i][j]: j = lane&15, i = (lane>>4)*4 + r  (r = 0..3, fp32)
-// `mfma_probe` below verifies this mapping numerically on device.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+// MFMA: v_mfma_f32_16x16x32_bf16; lane maps, fragment reads and the
+// block mapping are in mfma.h (`mfma_probe` / `tr16_probe` below verify
+// them numerically on device).
+#include "mfma.h"
 
 #define QBLK 128     // queries per workgroup (8 waves x 16 rows)
 #define AV_WAVES 8
@@ -27,59 +23,32 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define KVBLK 64     // keys per LDS tile
 #define HDMAX 128
 #define KPAD 8       // K tile row pad (bf16 elems)
-#define VPAD 8       // vT tile row pad
+#define VPAD 8       // P tile row pad
+// V stays ROW-major: the PV B-fragment is gathered by the hardware
+// transpose read (tr16_bfrag, mfma.h).  16 elems of row pad keep the four
+// row-steps on distinct bank sets.
+#define VROWPAD 16
 
-DEVINL float group16_max(float x) {
-  // reduce over the 16 lanes that share lane>>4
-  x = fmaxf(x, __shfl_xor(x, 1, 64));
-  x = fmaxf(x, __shfl_xor(x, 2, 64));
-  x = fmaxf(x, __shfl_xor(x, 4, 64));
-  x = fmaxf(x, __shfl_xor(x, 8, 64));
-  return x;
-}
-DEVINL float group16_sum(float x) {
-  x += __shfl_xor(x, 1, 64);
-  x += __shfl_xor(x, 2, 64);
-  x += __shfl_xor(x, 4, 64);
-  x += __shfl_xor(x, 8, 64);
-  return x;
-}
-
-
-// ---------------------------------------------------------------------------
-// Device-side block mapping: blk_offsets[i] = sum_{j<i} ceil(L_j / blk).
-// Built by a tiny kernel each call so the host NEVER reads cu_seqlens
-// (the old host-built block list cost one DtoH sync per layer call in
-// training — VERDICT round-1 weak item).  Workgroups past the real block
-// count exit immediately; the grid is the cheap upper bound
-// total/blk + bs.
-// ---------------------------------------------------------------------------
-static __global__ void build_blk_offsets_kernel(const int* __restrict__ cu, int bs,
-                                         int blk, int* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    int acc = 0;
-    for (int i = 0; i < bs; i++) {
-      out[i] = acc;
-      int L = cu[i + 1] - cu[i];
-      acc += (L + blk - 1) / blk;
-    }
-    out[bs] = acc;
-  }
-}
-
-DEVINL int blk_lookup(const int* __restrict__ off, int bs, int blk_id) {
-  int lo = 0, hi = bs;  // largest i with off[i] <= blk_id
-  while (lo + 1 < hi) {
-    int mid = (lo + hi) >> 1;
-    if (off[mid] <= blk_id) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4v;
-typedef __attribute__((address_space(3))) bf16x4v lds_b64_t;
-
-template <int HD>
+// One kernel, two staging schemes (DB).  Everything but the staging and
+// its barriers — block mapping, Q fragments, the per-tile S/softmax/PV body,
+// the epilogue — is written once.  It is one kernel body and not a set of
+// inlined helper functions on purpose: behind a function boundary the tile
+// body compiles to different code for the default scheme (hd=64: 95 -> 98
+// VGPRs, 5 -> 4 waves/SIMD); `if constexpr` leaves it untouched.
+//
+// DB = false (default): each 64-key tile is staged into one LDS buffer
+// between two barriers, and a third barrier separates the P store from PV.
+//
+// DB = true: double-buffered long-context variant.  KV tiles ping-pong
+// through two LDS buffers; tile i+1's global loads issue BEFORE tile i's
+// compute and the LDS writes land after it, so the HBM/L2 stream overlaps
+// the MFMA+softmax phases and the per-tile barriers collapse to one.
+// ~90 KB LDS (2x KV tiles + P), still one workgroup per CU.  MEASURED
+// SLOWER at every shape (317 vs 387 TF/s at 32k): the staging registers +
+// larger LDS hurt more than the saved barrier+overlap help.  Kept behind
+// REALHF_AMD_ATTN_DB=1 as the baseline for future pipelining work;
+// default always uses the single-buffer scheme.
+template <int HD, bool DB>
 __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const int* __restrict__ cu_seqlens,
@@ -87,6 +56,7 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
     bf16* __restrict__ out, float* __restrict__ lse,
     int nq, int nkv, float scale, bool causal, int window) {
   constexpr int HDCH = HD / 32;  // mfma K-chunks over head_dim
+  constexpr int NBUF = DB ? 2 : 1;
   const int blk = blockIdx.x;
   if (blk >= blk_offsets[n_seqs]) return;  // over-provisioned grid tail
   const int qh = blockIdx.y;
@@ -95,20 +65,10 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
   const int q0_local = (blk - blk_offsets[seq]) * QBLK;  // local query start
   const int s0 = cu_seqlens[seq], s1 = cu_seqlens[seq + 1];
   const int L = s1 - s0;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int i16 = lane & 15;   // A-row / B-col / C-col index
-  const int g = lane >> 4;     // k-chunk group / C row group
+  const auto [lane, w, i16, g] = mfma_lane();
 
-  __shared__ __bf16 k_s[KVBLK][HD + KPAD];
-  // V stays ROW-major: the PV B-fragment is gathered by the hardware
-  // transpose read ds_read_b64_tr_b16 (mapping derived by tr16_probe:
-  // in each 16-lane group, result lane c elem j = source-lane
-  // (4j + c/4)'s element (c%4); so lane i loading the 8-byte chunk at
-  // v_s[kbase + 4t + i/4][hd0 + (i%4)*4] makes the group end up with
-  // exactly B[k = 4t + j][n = c]).  VROWPAD = 16 elems keeps the four
-  // row-steps on distinct bank sets.
-  __shared__ __bf16 v_s[KVBLK][HD + 16];
+  __shared__ __bf16 k_s[NBUF][KVBLK][HD + KPAD];
+  __shared__ __bf16 v_s[NBUF][KVBLK][HD + VROWPAD];
   __shared__ __bf16 p_s[AV_WAVES][QW][KVBLK + VPAD];
 
   // ---- load Q fragments (registers, whole kernel) --------------------
@@ -140,24 +100,69 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
     kv_begin = (kv_begin > 0) ? (kv_begin / KVBLK) * KVBLK : 0;
   }
 
-  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KVBLK) {
-    const int kchunk = min(KVBLK, kv_end - kv0);
-    // ---- stage K and V(T) tiles ------------------------------------
-    __syncthreads();
-    // K: 64 rows x HD; all waves stage cooperatively, 16B per thread
-    for (int idx = threadIdx.x; idx < KVBLK * (HD / 8); idx += 64 * AV_WAVES) {
+  // DB only: each thread holds SLOTS 8-elem groups of the next 64 x HD
+  // tile per tensor in registers while the current tile computes
+  constexpr int SLOTS = DB ? (KVBLK * (HD / 8) + 64 * AV_WAVES - 1) /
+                                 (64 * AV_WAVES)
+                           : 1;
+  bf16x8 kreg[SLOTS], vreg[SLOTS];
+  auto load_tile = [&](int kv0) {
+    #pragma unroll
+    for (int s = 0; s < SLOTS; s++) {
+      int idx = threadIdx.x + s * 64 * AV_WAVES;
+      if (idx >= KVBLK * (HD / 8)) break;
       int row = idx / (HD / 8);
       int col8 = (idx % (HD / 8)) * 8;
-      bf16x8 val = {};
-      bf16x8 vv = {};
-      if (row < kchunk) {
-        val = *(const bf16x8*)(k + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
-        vv = *(const bf16x8*)(v + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
+      bf16x8 kv8 = {}, vv8 = {};
+      if (row < kv_end - kv0) {
+        kv8 = *(const bf16x8*)(k + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
+        vv8 = *(const bf16x8*)(v + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
       }
-      *(bf16x8*)(&k_s[row][col8]) = val;
-      *(bf16x8*)(&v_s[row][col8]) = vv;
+      kreg[s] = kv8;
+      vreg[s] = vv8;
     }
+  };
+  auto store_tile = [&](int buf) {
+    #pragma unroll
+    for (int s = 0; s < SLOTS; s++) {
+      int idx = threadIdx.x + s * 64 * AV_WAVES;
+      if (idx >= KVBLK * (HD / 8)) break;
+      int row = idx / (HD / 8);
+      int col8 = (idx % (HD / 8)) * 8;
+      *(bf16x8*)(&k_s[buf][row][col8]) = kreg[s];
+      *(bf16x8*)(&v_s[buf][row][col8]) = vreg[s];
+    }
+  };
+  if constexpr (DB) {
+    load_tile(kv_begin);
+    store_tile(0);
     __syncthreads();
+  }
+
+  int cur = 0;  // LDS buffer holding this tile (always 0 without DB)
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += KVBLK) {
+    if constexpr (DB) {
+      if (kv0 + KVBLK < kv_end)
+        load_tile(kv0 + KVBLK);  // global loads in flight during compute
+    } else {
+      const int kchunk = min(KVBLK, kv_end - kv0);
+      // ---- stage K and V tiles -------------------------------------
+      __syncthreads();
+      // 64 rows x HD; all waves stage cooperatively, 16B per thread
+      for (int idx = threadIdx.x; idx < KVBLK * (HD / 8); idx += 64 * AV_WAVES) {
+        int row = idx / (HD / 8);
+        int col8 = (idx % (HD / 8)) * 8;
+        bf16x8 val = {};
+        bf16x8 vv = {};
+        if (row < kchunk) {
+          val = *(const bf16x8*)(k + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
+          vv = *(const bf16x8*)(v + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
+        }
+        *(bf16x8*)(&k_s[0][row][col8]) = val;
+        *(bf16x8*)(&v_s[0][row][col8]) = vv;
+      }
+      __syncthreads();
+    }
 
     // ---- S = Q K^T over 4 key subtiles ------------------------------
     f32x4 s_sub[4];
@@ -167,8 +172,8 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
       #pragma unroll
       for (int c = 0; c < HDCH; c++) {
         // B fragment: K[key = ks*16 + i16][c*32 + g*8 + j]
-        bf16x8 bfrag = *(const bf16x8*)(&k_s[ks * 16 + i16][c * 32 + g * 8]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[c], bfrag, acc, 0, 0, 0);
+        bf16x8 bfrag = *(const bf16x8*)(&k_s[cur][ks * 16 + i16][c * 32 + g * 8]);
+        acc = mfma16(qfrag[c], bfrag, acc);
       }
       s_sub[ks] = acc;
     }
@@ -216,7 +221,9 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
       for (int r = 0; r < 4; r++)
         p_s[w][g * 4 + r][ks * 16 + i16] = (__bf16)s_sub[ks][r];
     }
-    __syncthreads();
+    // p_s is per-wave (written and read by the same wave); the DB scheme
+    // relies on same-wave LDS ordering and has no barrier here
+    if constexpr (!DB) __syncthreads();
 
     // ---- O += P V ----------------------------------------------------
     #pragma unroll
@@ -227,220 +234,24 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
       const int vcol4 = (i16 & 3) * 4;
       #pragma unroll
       for (int t = 0; t < HD / 16; t++) {
-        // B fragment via two hardware-transpose reads (see v_s comment)
-        bf16x4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (lds_b64_t*)&v_s[krow0][t * 16 + vcol4]);
-        bf16x4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (lds_b64_t*)&v_s[krow0 + 4][t * 16 + vcol4]);
+        // B fragment as in tr16_bfrag (mfma.h), on the typed tile: through
+        // the helper's flat pointer the LDS offsets fold differently and
+        // the register allocation of this kernel changes
+        bf16x4 r0 = tr16_read(&v_s[cur][krow0][t * 16 + vcol4]);
+        bf16x4 r1 = tr16_read(&v_s[cur][krow0 + 4][t * 16 + vcol4]);
         bf16x8 vb;
         #pragma unroll
         for (int j = 0; j < 4; j++) { vb[j] = r0[j]; vb[4 + j] = r1[j]; }
-        o_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, o_acc[t], 0, 0, 0);
-      }
-    }
-  }
-
-  // ---- epilogue ------------------------------------------------------
-  #pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const int qrow = q0_local + w * QW + g * 4 + r;
-    if (qrow >= L) continue;
-    float inv = (l_r[r] > 0.f) ? 1.f / l_r[r] : 0.f;
-    bf16* orow = out + ((long)(s0 + qrow) * nq + qh) * HD;
-    #pragma unroll
-    for (int t = 0; t < HD / 16; t++)
-      orow[t * 16 + i16] = __float2bfloat16(o_acc[t][r] * inv);
-    if (lse && i16 == 0)
-      lse[(long)(s0 + qrow) * nq + qh] = m_r[r] + __logf(fmaxf(l_r[r], 1e-30f));
-  }
-}
-
-
-// ---------------------------------------------------------------------------
-// Double-buffered long-context variant: KV tiles ping-pong through two LDS
-// buffers; block i+1's global loads issue BEFORE block i's compute and the
-// LDS writes land after it, so the HBM/L2 stream overlaps the MFMA+softmax
-// phases and the two per-block __syncthreads collapse to one.  ~90 KB LDS
-// (2x KV tiles + P), still one workgroup per CU.  MEASURED SLOWER at
-// every shape (317 vs 387 TF/s at 32k): the staging registers + larger
-// LDS hurt more than the saved barrier+overlap help.  Kept behind
-// REALHF_AMD_ATTN_DB=1 as the baseline for future pipelining work;
-// default always uses the single-buffer kernel.
-template <int HD>
-__global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_db_kernel(
-    const bf16* __restrict__ q, const bf16* __restrict__ k,
-    const bf16* __restrict__ v, const int* __restrict__ cu_seqlens,
-    const int* __restrict__ blk_offsets, int n_seqs,
-    bf16* __restrict__ out, float* __restrict__ lse,
-    int nq, int nkv, float scale, bool causal, int window) {
-  constexpr int HDCH = HD / 32;
-  const int blk = blockIdx.x;
-  if (blk >= blk_offsets[n_seqs]) return;
-  const int qh = blockIdx.y;
-  const int kvh = qh / (nq / nkv);
-  const int seq = blk_lookup(blk_offsets, n_seqs, blk);
-  const int q0_local = (blk - blk_offsets[seq]) * QBLK;
-  const int s0 = cu_seqlens[seq], s1 = cu_seqlens[seq + 1];
-  const int L = s1 - s0;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int i16 = lane & 15;
-  const int g = lane >> 4;
-
-  __shared__ __bf16 k_s[2][KVBLK][HD + KPAD];
-  __shared__ __bf16 v_s[2][KVBLK][HD + 16];
-  __shared__ __bf16 p_s[AV_WAVES][QW][KVBLK + VPAD];
-
-  bf16x8 qfrag[HDCH];
-  const int my_qrow_a = q0_local + w * QW + i16;
-  {
-    const bf16* qrow = q + ((long)(s0 + min(my_qrow_a, L - 1)) * nq + qh) * HD;
-    #pragma unroll
-    for (int c = 0; c < HDCH; c++)
-      qfrag[c] = *(const bf16x8*)(qrow + c * 32 + g * 8);
-  }
-
-  float m_r[4], l_r[4];
-  f32x4 o_acc[HD / 16];
-  #pragma unroll
-  for (int r = 0; r < 4; r++) { m_r[r] = -1e30f; l_r[r] = 0.f; }
-  #pragma unroll
-  for (int t = 0; t < HD / 16; t++) o_acc[t] = {0.f, 0.f, 0.f, 0.f};
-
-  const int kv_end = causal ? min(L, q0_local + QBLK) : L;
-  int kv_begin = 0;
-  if (window > 0) {
-    kv_begin = q0_local - window + 1;
-    kv_begin = (kv_begin > 0) ? (kv_begin / KVBLK) * KVBLK : 0;
-  }
-  const int nblocks = (kv_end - kv_begin + KVBLK - 1) / KVBLK;
-  if (nblocks <= 0) return;
-
-  // each thread stages SLOTS 8-elem groups of the 64 x HD tile per tensor
-  constexpr int SLOTS = (KVBLK * (HD / 8)) / (64 * AV_WAVES) > 0
-                            ? (KVBLK * (HD / 8) + 64 * AV_WAVES - 1) /
-                                  (64 * AV_WAVES)
-                            : 1;
-  bf16x8 kreg[SLOTS], vreg[SLOTS];
-
-  auto load_tile = [&](int kv0) {
-    #pragma unroll
-    for (int s = 0; s < SLOTS; s++) {
-      int idx = threadIdx.x + s * 64 * AV_WAVES;
-      if (idx >= KVBLK * (HD / 8)) break;
-      int row = idx / (HD / 8);
-      int col8 = (idx % (HD / 8)) * 8;
-      bf16x8 kv8 = {}, vv8 = {};
-      if (row < kv_end - kv0) {
-        kv8 = *(const bf16x8*)(k + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
-        vv8 = *(const bf16x8*)(v + ((long)(s0 + kv0 + row) * nkv + kvh) * HD + col8);
-      }
-      kreg[s] = kv8;
-      vreg[s] = vv8;
-    }
-  };
-  auto store_tile = [&](int buf) {
-    #pragma unroll
-    for (int s = 0; s < SLOTS; s++) {
-      int idx = threadIdx.x + s * 64 * AV_WAVES;
-      if (idx >= KVBLK * (HD / 8)) break;
-      int row = idx / (HD / 8);
-      int col8 = (idx % (HD / 8)) * 8;
-      *(bf16x8*)(&k_s[buf][row][col8]) = kreg[s];
-      *(bf16x8*)(&v_s[buf][row][col8]) = vreg[s];
-    }
-  };
-
-  load_tile(kv_begin);
-  store_tile(0);
-  __syncthreads();
-
-  for (int b = 0; b < nblocks; b++) {
-    const int kv0 = kv_begin + b * KVBLK;
-    const int cur = b & 1;
-    if (b + 1 < nblocks)
-      load_tile(kv0 + KVBLK);  // global loads in flight during compute
-
-    // ---- S = Q K^T over 4 key subtiles -----------------------------
-    f32x4 s_sub[4];
-    #pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      #pragma unroll
-      for (int c = 0; c < HDCH; c++) {
-        bf16x8 bfrag = *(const bf16x8*)(&k_s[cur][ks * 16 + i16][c * 32 + g * 8]);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfrag[c], bfrag, acc, 0, 0, 0);
-      }
-      s_sub[ks] = acc;
-    }
-
-    // ---- softmax ----------------------------------------------------
-    float tile_max[4];
-    #pragma unroll
-    for (int r = 0; r < 4; r++) {
-      float mx = -1e30f;
-      const int qrow = q0_local + w * QW + g * 4 + r;
-      #pragma unroll
-      for (int ks = 0; ks < 4; ks++) {
-        int kidx = kv0 + ks * 16 + i16;
-        bool ok = (kidx < kv_end) && (!causal || kidx <= qrow) && (qrow < L)
-                  && (window <= 0 || kidx > qrow - window);
-        float sv = ok ? s_sub[ks][r] * scale : -1e30f;
-        s_sub[ks][r] = sv;
-        mx = fmaxf(mx, sv);
-      }
-      tile_max[r] = group16_max(mx);
-    }
-    #pragma unroll
-    for (int r = 0; r < 4; r++) {
-      float nm = fmaxf(m_r[r], tile_max[r]);
-      if (nm < -1e29f) nm = 0.f;
-      float f = __expf(m_r[r] - nm);
-      if (m_r[r] < -1e29f) f = 0.f;
-      m_r[r] = nm;
-      l_r[r] *= f;
-      #pragma unroll
-      for (int t = 0; t < HD / 16; t++) o_acc[t][r] *= f;
-      float rowsum = 0.f;
-      #pragma unroll
-      for (int ks = 0; ks < 4; ks++) {
-        float p = (s_sub[ks][r] > -1e29f) ? __expf(s_sub[ks][r] - nm) : 0.f;
-        s_sub[ks][r] = p;
-        rowsum += p;
-      }
-      l_r[r] += group16_sum(rowsum);
-    }
-    #pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      #pragma unroll
-      for (int r = 0; r < 4; r++)
-        p_s[w][g * 4 + r][ks * 16 + i16] = (__bf16)s_sub[ks][r];
-    }
-    // p_s is per-wave (written and read by the same wave): same-wave LDS
-    // ordering makes it visible without a barrier
-
-    // ---- O += P V ---------------------------------------------------
-    #pragma unroll
-    for (int kk = 0; kk < 2; kk++) {
-      bf16x8 pa = *(const bf16x8*)(&p_s[w][i16][kk * 32 + g * 8]);
-      const int krow0 = kk * 32 + g * 8 + (i16 >> 2);
-      const int vcol4 = (i16 & 3) * 4;
-      #pragma unroll
-      for (int t = 0; t < HD / 16; t++) {
-        bf16x4v r0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (lds_b64_t*)&v_s[cur][krow0][t * 16 + vcol4]);
-        bf16x4v r1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (lds_b64_t*)&v_s[cur][krow0 + 4][t * 16 + vcol4]);
-        bf16x8 vb;
-        #pragma unroll
-        for (int j = 0; j < 4; j++) { vb[j] = r0[j]; vb[4 + j] = r1[j]; }
-        o_acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, o_acc[t], 0, 0, 0);
+        o_acc[t] = mfma16(pa, vb, o_acc[t]);
       }
     }
 
-    if (b + 1 < nblocks) {
-      store_tile(cur ^ 1);  // other buffer: no hazard with this block
-      __syncthreads();      // publish before every wave's next S phase
+    if constexpr (DB) {
+      if (kv0 + KVBLK < kv_end) {
+        store_tile(cur ^ 1);  // other buffer: no hazard with this tile
+        __syncthreads();      // publish before every wave's next S phase
+      }
+      cur ^= 1;
     }
   }
 
@@ -479,10 +290,7 @@ std::vector<torch::Tensor> attn_varlen_fwd(
   TORCH_CHECK(nq % nkv == 0);
   auto cu_dev = cu_seqlens.to(torch::kInt).to(q.device());
   int bs = cu_dev.numel() - 1;
-  auto opts = torch::TensorOptions().dtype(torch::kInt).device(q.device());
-  auto blk_off = torch::empty({(long)bs + 1}, opts);
-  hipLaunchKernelGGL(build_blk_offsets_kernel, dim3(1), dim3(64), 0,
-    cur_stream(), cu_dev.data_ptr<int>(), bs, QBLK, blk_off.data_ptr<int>());
+  auto blk_off = build_blk_offsets<QBLK>(cu_dev);
   auto out = torch::empty_like(q);
   auto lse = torch::empty({total, nq}, q.options().dtype(torch::kFloat));
   // upper bound on sum(ceil(L/QBLK)) — real tail blocks exit on the
@@ -490,35 +298,20 @@ std::vector<torch::Tensor> attn_varlen_fwd(
   dim3 grid((unsigned)(total / QBLK + bs), nq);
   int dbm = attn_db_mode();
   bool use_db = (dbm == 1) || (dbm == -1 && max_seqlen >= 4096);
+  TORCH_CHECK(hd == 128 || hd == 64, "unsupported head_dim ", hd);
+#define FW_LAUNCH(HD_, DB_)                                               \
+  hipLaunchKernelGGL((attn_varlen_fwd_kernel<HD_, DB_>), grid,            \
+    dim3(64 * AV_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
+    (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),                 \
+    cu_dev.data_ptr<int>(), blk_off.data_ptr<int>(), bs,                  \
+    (bf16*)out.data_ptr(), lse.data_ptr<float>(), nq, nkv, (float)scale,  \
+    causal, (int)window)
   if (hd == 128) {
-    if (use_db)
-      hipLaunchKernelGGL((attn_varlen_fwd_db_kernel<128>), grid, dim3(64 * AV_WAVES), 0,
-        cur_stream(), (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
-        (const bf16*)v.data_ptr(), cu_dev.data_ptr<int>(),
-        blk_off.data_ptr<int>(), bs, (bf16*)out.data_ptr(),
-        lse.data_ptr<float>(), nq, nkv, (float)scale, causal, (int)window);
-    else
-      hipLaunchKernelGGL((attn_varlen_fwd_kernel<128>), grid, dim3(64 * AV_WAVES), 0,
-        cur_stream(), (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
-        (const bf16*)v.data_ptr(), cu_dev.data_ptr<int>(),
-        blk_off.data_ptr<int>(), bs, (bf16*)out.data_ptr(),
-        lse.data_ptr<float>(), nq, nkv, (float)scale, causal, (int)window);
-  } else if (hd == 64) {
-    if (use_db)
-      hipLaunchKernelGGL((attn_varlen_fwd_db_kernel<64>), grid, dim3(64 * AV_WAVES), 0,
-        cur_stream(), (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
-        (const bf16*)v.data_ptr(), cu_dev.data_ptr<int>(),
-        blk_off.data_ptr<int>(), bs, (bf16*)out.data_ptr(),
-        lse.data_ptr<float>(), nq, nkv, (float)scale, causal, (int)window);
-    else
-      hipLaunchKernelGGL((attn_varlen_fwd_kernel<64>), grid, dim3(64 * AV_WAVES), 0,
-        cur_stream(), (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(),
-        (const bf16*)v.data_ptr(), cu_dev.data_ptr<int>(),
-        blk_off.data_ptr<int>(), bs, (bf16*)out.data_ptr(),
-        lse.data_ptr<float>(), nq, nkv, (float)scale, causal, (int)window);
+    if (use_db) FW_LAUNCH(128, true); else FW_LAUNCH(128, false);
   } else {
-    TORCH_CHECK(false, "unsupported head_dim ", hd);
+    if (use_db) FW_LAUNCH(64, true); else FW_LAUNCH(64, false);
   }
+#undef FW_LAUNCH
   CHECK_CUDA_OK();
   return {out, lse};
 }
@@ -529,16 +322,14 @@ std::vector<torch::Tensor> attn_varlen_fwd(
 // ASYMMETRIC B").
 // ---------------------------------------------------------------------------
 __global__ void mfma_probe_kernel(const bf16* A, const bf16* B, float* D) {
-  int lane = threadIdx.x & 63;
-  int i16 = lane & 15, g = lane >> 4;
+  const auto [lane, w, i16, g] = mfma_lane();
   bf16x8 a, b;
   #pragma unroll
   for (int j = 0; j < 8; j++) {
     a[j] = (__bf16)A[i16 * 32 + g * 8 + j];      // A[i][k] row-major
     b[j] = (__bf16)B[(g * 8 + j) * 16 + i16];    // B[k][n] row-major
   }
-  f32x4 c = {0.f, 0.f, 0.f, 0.f};
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  f32x4 c = mfma16(a, b, f32x4{0.f, 0.f, 0.f, 0.f});
   #pragma unroll
   for (int r = 0; r < 4; r++) D[(g * 4 + r) * 16 + i16] = c[r];
 }
@@ -556,7 +347,7 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
 }
 
 // ---------------------------------------------------------------------------
-// tr16_probe: empirical map of ds_read_b64_tr_b16 — each lane passes
+// tr16_probe: empirical map of tr16_read (mfma.h) — each lane passes
 // addr = lds_base + 2*addr_elem[lane] (bf16 elems); the kernel stages
 // lds[i] = i and dumps what (lane, j) receives, so the host can derive
 // the lane->element mapping for MFMA B-fragment use (guide §2 T10).
@@ -564,12 +355,11 @@ torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
 __global__ void tr16_probe_kernel(const int* __restrict__ addr_elem,
                                   float* __restrict__ out) {
   __shared__ __bf16 lds[1024];
-  int lane = threadIdx.x & 63;
+  const int lane = mfma_lane().lane;
   for (int i = threadIdx.x; i < 1024; i += 64)
     lds[i] = (__bf16)(float)i;
   __syncthreads();
-  bf16x4v r = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_b64_t*)&lds[addr_elem[lane]]);
+  bf16x4 r = tr16_read(&lds[addr_elem[lane]]);
   #pragma unroll
   for (int j = 0; j < 4; j++) out[lane * 4 + j] = (float)r[j];
 }

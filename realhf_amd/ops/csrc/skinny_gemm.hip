@@ -9,12 +9,50 @@
 // streamed straight into MFMA B-fragments (16 B/lane loads, one pass,
 // nothing cached); fp32 split-K partials combined with global atomics;
 // a trailing kernel converts to bf16.
-#include "common.h"
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
+// MFMA lane maps: mfma.h.
+#include "mfma.h"
 
 #define SG_TN 64  // n per workgroup (16 per wave)
+
+// x_s[16][kslice] <- x[0..M)[k_lo..k_hi), zero-padded (m >= M, k >= k_hi);
+// NT = threads per workgroup
+template <int NT>
+DEVINL void sg_stage_x(__bf16* x_s, const bf16* __restrict__ x, int M, int K,
+                       int k_lo, int k_hi, int kslice) {
+  const int kn = k_hi - k_lo;
+  for (int idx = threadIdx.x * 8; idx < 16 * kslice; idx += NT * 8) {
+    int m = idx / kslice;
+    int kk = idx % kslice;
+    bf16x8 v = {};
+    if (kk < kn && m < M)
+      v = *(const bf16x8*)(x + (long)m * K + k_lo + kk);
+    *(bf16x8*)(&x_s[(long)m * kslice + kk]) = v;
+  }
+}
+
+// out[off..off+4) = bf16(sum over the nks fp32 slabs at parts + s*slab + off
+// (+ resid[off..off+4))), one 8-byte store
+DEVINL void sg_reduce_store(const float* __restrict__ parts, long slab,
+                            int nks, long off, const bf16* __restrict__ resid,
+                            bf16* __restrict__ out) {
+  f32x4 v = *(const f32x4*)(parts + off);
+  for (int s = 1; s < nks; s++) {
+    f32x4 p = *(const f32x4*)(parts + (long)s * slab + off);
+    #pragma unroll
+    for (int j = 0; j < 4; j++) v[j] += p[j];
+  }
+  short o[4];
+  if (resid) {
+    short4v rv = *(const short4v*)((const short*)resid + off);
+    #pragma unroll
+    for (int j = 0; j < 4; j++)
+      o[j] = f2bf(v[j] + __bfloat162float(((const bf16*)&rv)[j]));
+  } else {
+    #pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = f2bf(v[j]);
+  }
+  *(short4v*)((short*)out + off) = *(short4v*)o;
+}
 
 // NB x 32-deep k body: NB 16-byte W loads in flight/lane.  WVS = waves
 // per workgroup (n-tile = WVS*16): 4 (=SG_TN 64) default; 2 halves the
@@ -28,24 +66,11 @@ __global__ __launch_bounds__(64 * WVS, 4) void skinny_gemm_kernel(
   const int ks = blockIdx.y;
   const int k_lo = ks * kslice;
   const int k_hi = min(K, k_lo + kslice);
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  const int i16 = lane & 15;
-  const int g = lane >> 4;
+  const auto [lane, wv, i16, g] = mfma_lane();
   const int n0 = ntile * (WVS * 16) + wv * 16;
 
   extern __shared__ __bf16 x_s[];  // [16][kslice] rows (zero-padded m >= M)
-  {
-    const int kn = k_hi - k_lo;
-    for (int idx = threadIdx.x * 8; idx < 16 * kslice; idx += 64 * WVS * 8) {
-      int m = idx / kslice;
-      int kk = idx % kslice;
-      bf16x8v v = {};
-      if (kk < kn && m < M)
-        v = *(const bf16x8v*)(x + (long)m * K + k_lo + kk);
-      *(bf16x8v*)(&x_s[(long)m * kslice + kk]) = v;
-    }
-  }
+  sg_stage_x<64 * WVS>(x_s, x, M, K, k_lo, k_hi, kslice);
   __syncthreads();
 
   // 4 rotating accumulators relax the MFMA RAW chain (PMC: 35%
@@ -57,23 +82,22 @@ __global__ __launch_bounds__(64 * WVS, 4) void skinny_gemm_kernel(
   // 16B loads stay in flight per lane (one k-iter alone is latency-bound)
   // (nt loads measured 15-40% SLOWER here — keep plain loads)
   for (; kk + NB * 32 <= k_hi; kk += NB * 32) {
-    bf16x8v b[NB], a[NB];
+    bf16x8 b[NB], a[NB];
     #pragma unroll
     for (int t = 0; t < NB; t++)
-      b[t] = *(const bf16x8v*)(wrow + kk + t * 32 + g * 8);
+      b[t] = *(const bf16x8*)(wrow + kk + t * 32 + g * 8);
     const long xb = (long)i16 * kslice + (kk - k_lo) + g * 8;
     #pragma unroll
     for (int t = 0; t < NB; t++)
-      a[t] = *(const bf16x8v*)(&x_s[xb + t * 32]);
+      a[t] = *(const bf16x8*)(&x_s[xb + t * 32]);
     #pragma unroll
     for (int t = 0; t < NB; t++)
-      acc[t & 3] =
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b[t], acc[t & 3], 0, 0, 0);
+      acc[t & 3] = mfma16(a[t], b[t], acc[t & 3]);
   }
   for (; kk + 32 <= k_hi; kk += 32) {
-    bf16x8v a0 = *(const bf16x8v*)(&x_s[(long)i16 * kslice + (kk - k_lo) + g * 8]);
-    bf16x8v b0 = *(const bf16x8v*)(wrow + kk + g * 8);
-    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[0], 0, 0, 0);
+    bf16x8 a0 = *(const bf16x8*)(&x_s[(long)i16 * kslice + (kk - k_lo) + g * 8]);
+    bf16x8 b0 = *(const bf16x8*)(wrow + kk + g * 8);
+    acc[0] = mfma16(a0, b0, acc[0]);
   }
   // non-atomic per-K-slice partial: out32[ks][m][n]
   #pragma unroll
@@ -107,37 +131,13 @@ static int sg_tn32_maxn() {
   return v;
 }
 
-template <typename F4, typename F8, typename F4w2, typename F8w2>
-static void sg_dispatch(int N, F4 f4, F8 f8, F4w2 f4w2, F8w2 f8w2) {
-  bool tn32 = N <= sg_tn32_maxn() && (N % 32) == 0;
-  if (sg_depth() == 8) { if (tn32) f8w2(); else f8(); }
-  else { if (tn32) f4w2(); else f4(); }
-}
-
 // combine the nks fp32 partial slabs -> bf16 (+ optional residual add)
 __global__ void sg_combine_kernel(const float* __restrict__ parts,
                                   const bf16* __restrict__ resid,
                                   bf16* __restrict__ out, long n, int nks) {
   for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n;
-       i += (long)gridDim.x * blockDim.x * 4) {
-    float4v v = *(const float4v*)(parts + i);
-    for (int s = 1; s < nks; s++) {
-      float4v p = *(const float4v*)(parts + (long)s * n + i);
-      #pragma unroll
-      for (int j = 0; j < 4; j++) v[j] += p[j];
-    }
-    short o[4];
-    if (resid) {
-      short4v rv = *(const short4v*)((const short*)resid + i);
-      #pragma unroll
-      for (int j = 0; j < 4; j++)
-        o[j] = f2bf(v[j] + __bfloat162float(((const bf16*)&rv)[j]));
-    } else {
-      #pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = f2bf(v[j]);
-    }
-    *(short4v*)((short*)out + i) = *(short4v*)o;
-  }
+       i += (long)gridDim.x * blockDim.x * 4)
+    sg_reduce_store(parts, n, nks, i, resid, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -146,33 +146,60 @@ __global__ void sg_combine_kernel(const float* __restrict__ parts,
 // reduce, guide split-K recipe: "combine in the NEXT kernel's prologue
 // ... costs nothing extra when that kernel exists anyway").  Consumers:
 // rope_qkv_decode / add_rmsnorm_fwd / swiglu_fwd slab modes.
-torch::Tensor skinny_gemm_nc(torch::Tensor x, torch::Tensor w,
-                             torch::Tensor out32_ws, long splitk) {
+struct SgShape { int M, N, K, kslice, nks; size_t lds; };
+
+// x [M, K] bf16; w [N, K] bf16 (row-major view, stride(1)==1);
+// out32_ws: fp32 workspace >= nks * M * N (per-slice partials — no
+// zeroing, no atomics)
+static SgShape sg_shape(const torch::Tensor& x, const torch::Tensor& w,
+                        const torch::Tensor& out32_ws, long splitk) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1);
   TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1);
-  int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M <= 16 && K % 32 == 0 && N % SG_TN == 0);
-  TORCH_CHECK(x.stride(0) == K, "x must be contiguous");
-  int kslice = (K / (int)splitk + 63) / 64 * 64;
-  int nks = (K + kslice - 1) / kslice;
-  TORCH_CHECK(out32_ws.numel() >= (long)nks * M * N, "workspace too small");
-  auto out32 = out32_ws.narrow(0, 0, (long)nks * M * N)
-                   .view({(long)nks, (long)M, (long)N});
-  size_t lds = (size_t)16 * kslice * sizeof(short);
-  TORCH_CHECK(lds <= 160 * 1024, "kslice too large for LDS");
+  SgShape s;
+  s.M = x.size(0); s.K = x.size(1); s.N = w.size(0);
+  TORCH_CHECK(s.M <= 16 && s.K % 32 == 0 && s.N % SG_TN == 0);
+  TORCH_CHECK(x.stride(0) == s.K, "x must be contiguous");
+  s.kslice = (s.K / (int)splitk + 63) / 64 * 64;
+  s.nks = (s.K + s.kslice - 1) / s.kslice;
+  TORCH_CHECK(out32_ws.numel() >= (long)s.nks * s.M * s.N, "workspace too small");
+  s.lds = (size_t)16 * s.kslice * sizeof(short);
+  TORCH_CHECK(s.lds <= 160 * 1024, "kslice too large for LDS");
+  return s;
+}
+
+// launch the split-K partial kernel; returns the [nks, M, N] slab view
+static torch::Tensor sg_partials(const torch::Tensor& x, const torch::Tensor& w,
+                                 const torch::Tensor& out32_ws,
+                                 const SgShape& s) {
+  auto out32 = out32_ws.narrow(0, 0, (long)s.nks * s.M * s.N)
+                   .view({(long)s.nks, (long)s.M, (long)s.N});
   auto launch = [&](auto nb, auto wvs) {
-    dim3 grid(N / (16 * wvs.value), nks);
+    dim3 grid(s.N / (16 * wvs.value), s.nks);
     hipLaunchKernelGGL((skinny_gemm_kernel<nb.value, wvs.value>), grid,
-      dim3(64 * wvs.value), lds, cur_stream(),
+      dim3(64 * wvs.value), s.lds, cur_stream(),
       (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
-      out32.data_ptr<float>(), M, N, K, kslice);
+      out32.data_ptr<float>(), s.M, s.N, s.K, s.kslice);
   };
   using c4 = std::integral_constant<int, 4>;
   using c8 = std::integral_constant<int, 8>;
   using c2 = std::integral_constant<int, 2>;
-  sg_dispatch(N, [&]{ launch(c4{}, c4{}); }, [&]{ launch(c8{}, c4{}); },
-              [&]{ launch(c4{}, c2{}); }, [&]{ launch(c8{}, c2{}); });
+  const bool tn32 = s.N <= sg_tn32_maxn() && (s.N % 32) == 0;
+  if (sg_depth() == 8) { if (tn32) launch(c8{}, c2{}); else launch(c8{}, c4{}); }
+  else { if (tn32) launch(c4{}, c2{}); else launch(c4{}, c4{}); }
+  return out32;
+}
+
+static const bf16* sg_resid_ptr(const c10::optional<torch::Tensor>& residual,
+                                long n) {
+  if (!residual.has_value()) return nullptr;
+  TORCH_CHECK(residual->is_contiguous() && residual->numel() == n);
+  return (const bf16*)residual->data_ptr();
+}
+
+torch::Tensor skinny_gemm_nc(torch::Tensor x, torch::Tensor w,
+                             torch::Tensor out32_ws, long splitk) {
+  auto out32 = sg_partials(x, w, out32_ws, sg_shape(x, w, out32_ws, splitk));
   CHECK_CUDA_OK();
   return out32;
 }
@@ -209,60 +236,47 @@ __global__ __launch_bounds__(256, 4) void skinny_gemm2_kernel(
   }
   const int k_lo = ks * kslice;
   const int k_hi = min(K, k_lo + kslice);
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  const int i16 = lane & 15;
-  const int g = lane >> 4;
+  const auto [lane, wv, i16, g] = mfma_lane();
   const int n0 = ntile * SG_TN + wv * 16;
 
   extern __shared__ __bf16 x_s[];  // [16][kslice] rows (zero-padded m >= M)
-  {
-    const int kn = k_hi - k_lo;
-    for (int idx = threadIdx.x * 8; idx < 16 * kslice; idx += 256 * 8) {
-      int m = idx / kslice;
-      int kk = idx % kslice;
-      bf16x8v v = {};
-      if (kk < kn && m < M)
-        v = *(const bf16x8v*)(x + (long)m * K + k_lo + kk);
-      *(bf16x8v*)(&x_s[(long)m * kslice + kk]) = v;
-    }
-  }
+  sg_stage_x<256>(x_s, x, M, K, k_lo, k_hi, kslice);
   __syncthreads();
 
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   const bf16* wrow = w + (long)(n0 + i16) * K;
   int kk = k_lo;
   for (; kk + 256 <= k_hi; kk += 256) {
-    bf16x8v b0 = *(const bf16x8v*)(wrow + kk + g * 8);
-    bf16x8v b1 = *(const bf16x8v*)(wrow + kk + 32 + g * 8);
-    bf16x8v b2 = *(const bf16x8v*)(wrow + kk + 64 + g * 8);
-    bf16x8v b3 = *(const bf16x8v*)(wrow + kk + 96 + g * 8);
-    bf16x8v b4 = *(const bf16x8v*)(wrow + kk + 128 + g * 8);
-    bf16x8v b5 = *(const bf16x8v*)(wrow + kk + 160 + g * 8);
-    bf16x8v b6 = *(const bf16x8v*)(wrow + kk + 192 + g * 8);
-    bf16x8v b7 = *(const bf16x8v*)(wrow + kk + 224 + g * 8);
+    bf16x8 b0 = *(const bf16x8*)(wrow + kk + g * 8);
+    bf16x8 b1 = *(const bf16x8*)(wrow + kk + 32 + g * 8);
+    bf16x8 b2 = *(const bf16x8*)(wrow + kk + 64 + g * 8);
+    bf16x8 b3 = *(const bf16x8*)(wrow + kk + 96 + g * 8);
+    bf16x8 b4 = *(const bf16x8*)(wrow + kk + 128 + g * 8);
+    bf16x8 b5 = *(const bf16x8*)(wrow + kk + 160 + g * 8);
+    bf16x8 b6 = *(const bf16x8*)(wrow + kk + 192 + g * 8);
+    bf16x8 b7 = *(const bf16x8*)(wrow + kk + 224 + g * 8);
     const long xb = (long)i16 * kslice + (kk - k_lo) + g * 8;
-    bf16x8v a0 = *(const bf16x8v*)(&x_s[xb]);
-    bf16x8v a1 = *(const bf16x8v*)(&x_s[xb + 32]);
-    bf16x8v a2 = *(const bf16x8v*)(&x_s[xb + 64]);
-    bf16x8v a3 = *(const bf16x8v*)(&x_s[xb + 96]);
-    bf16x8v a4 = *(const bf16x8v*)(&x_s[xb + 128]);
-    bf16x8v a5 = *(const bf16x8v*)(&x_s[xb + 160]);
-    bf16x8v a6 = *(const bf16x8v*)(&x_s[xb + 192]);
-    bf16x8v a7 = *(const bf16x8v*)(&x_s[xb + 224]);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b2, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, b3, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a4, b4, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a5, b5, acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a6, b6, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a7, b7, acc1, 0, 0, 0);
+    bf16x8 a0 = *(const bf16x8*)(&x_s[xb]);
+    bf16x8 a1 = *(const bf16x8*)(&x_s[xb + 32]);
+    bf16x8 a2 = *(const bf16x8*)(&x_s[xb + 64]);
+    bf16x8 a3 = *(const bf16x8*)(&x_s[xb + 96]);
+    bf16x8 a4 = *(const bf16x8*)(&x_s[xb + 128]);
+    bf16x8 a5 = *(const bf16x8*)(&x_s[xb + 160]);
+    bf16x8 a6 = *(const bf16x8*)(&x_s[xb + 192]);
+    bf16x8 a7 = *(const bf16x8*)(&x_s[xb + 224]);
+    acc0 = mfma16(a0, b0, acc0);
+    acc1 = mfma16(a1, b1, acc1);
+    acc0 = mfma16(a2, b2, acc0);
+    acc1 = mfma16(a3, b3, acc1);
+    acc0 = mfma16(a4, b4, acc0);
+    acc1 = mfma16(a5, b5, acc1);
+    acc0 = mfma16(a6, b6, acc0);
+    acc1 = mfma16(a7, b7, acc1);
   }
   for (; kk + 32 <= k_hi; kk += 32) {
-    bf16x8v a0 = *(const bf16x8v*)(&x_s[(long)i16 * kslice + (kk - k_lo) + g * 8]);
-    bf16x8v b0 = *(const bf16x8v*)(wrow + kk + g * 8);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc0, 0, 0, 0);
+    bf16x8 a0 = *(const bf16x8*)(&x_s[(long)i16 * kslice + (kk - k_lo) + g * 8]);
+    bf16x8 b0 = *(const bf16x8*)(wrow + kk + g * 8);
+    acc0 = mfma16(a0, b0, acc0);
   }
   // publish the fp32 slab with plain stores
   #pragma unroll
@@ -300,26 +314,9 @@ __global__ __launch_bounds__(256, 4) void skinny_gemm2_kernel(
   const int base_n = ntile * SG_TN;
   const int m = threadIdx.x >> 4;
   const int c4 = (threadIdx.x & 15) * 4;
-  if (m < M) {
-    const long off = (long)m * N + base_n + c4;
-    float4v vsum = *(const float4v*)(out32 + off);
-    for (int s = 1; s < nks; s++) {
-      float4v p = *(const float4v*)(out32 + (long)s * M * N + off);
-      #pragma unroll
-      for (int j = 0; j < 4; j++) vsum[j] += p[j];
-    }
-    short o4[4];
-    if (resid) {
-      short4v rv = *(const short4v*)((const short*)resid + off);
-      #pragma unroll
-      for (int j = 0; j < 4; j++)
-        o4[j] = f2bf(vsum[j] + __bfloat162float(((const bf16*)&rv)[j]));
-    } else {
-      #pragma unroll
-      for (int j = 0; j < 4; j++) o4[j] = f2bf(vsum[j]);
-    }
-    *(short4v*)((short*)out + off) = *(short4v*)o4;
-  }
+  if (m < M)
+    sg_reduce_store(out32, (long)M * N, nks, (long)m * N + base_n + c4, resid,
+                    out);
   // self-reset so the persistent sem buffer is zero for the next launch
   // (stream order makes this safe; the buffer is zeroed once at alloc)
   if (threadIdx.x == 0)
@@ -330,77 +327,34 @@ __global__ __launch_bounds__(256, 4) void skinny_gemm2_kernel(
 torch::Tensor skinny_gemm2(torch::Tensor x, torch::Tensor w,
                            torch::Tensor out32_ws, torch::Tensor sem,
                            long splitk, c10::optional<torch::Tensor> residual) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1);
-  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1);
-  int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M <= 16 && K % 32 == 0 && N % SG_TN == 0);
-  TORCH_CHECK(x.stride(0) == K, "x must be contiguous");
-  int kslice = (K / (int)splitk + 63) / 64 * 64;
-  int nks = (K + kslice - 1) / kslice;
-  TORCH_CHECK(out32_ws.numel() >= (long)nks * M * N, "workspace too small");
-  TORCH_CHECK(sem.scalar_type() == torch::kInt32 && sem.numel() >= N / SG_TN,
+  const SgShape s = sg_shape(x, w, out32_ws, splitk);
+  TORCH_CHECK(sem.scalar_type() == torch::kInt32 && sem.numel() >= s.N / SG_TN,
               "semaphore buffer too small (must be zero-initialized once)");
-  auto out = torch::empty({M, (long)N}, x.options());
-  const bf16* rptr = nullptr;
-  if (residual.has_value()) {
-    TORCH_CHECK(residual->is_contiguous() &&
-                residual->numel() == (long)M * N);
-    rptr = (const bf16*)residual->data_ptr();
-  }
-  dim3 grid((N / SG_TN) * nks);  // 1-D: kernel derives (tile, slice)
-  size_t lds = (size_t)16 * kslice * sizeof(short);
-  TORCH_CHECK(lds <= 160 * 1024, "kslice too large for LDS");
-  hipLaunchKernelGGL(skinny_gemm2_kernel, grid, dim3(256), lds, cur_stream(),
+  auto out = torch::empty({s.M, (long)s.N}, x.options());
+  const bf16* rptr = sg_resid_ptr(residual, (long)s.M * s.N);
+  dim3 grid((s.N / SG_TN) * s.nks);  // 1-D: kernel derives (tile, slice)
+  hipLaunchKernelGGL(skinny_gemm2_kernel, grid, dim3(256), s.lds, cur_stream(),
     (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
     out32_ws.data_ptr<float>(), sem.data_ptr<int>(), rptr,
-    (bf16*)out.data_ptr(), M, N, K, kslice, nks);
+    (bf16*)out.data_ptr(), s.M, s.N, s.K, s.kslice, s.nks);
   CHECK_CUDA_OK();
   return out;
 }
 
+// partials, then the combine kernel (residual, optional [M, N] bf16, is
+// folded into it)
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
                           torch::Tensor out32_ws, long splitk,
                           c10::optional<torch::Tensor> residual) {
-  // x [M, K] bf16; w [N, K] bf16 (row-major view, stride(1)==1);
-  // out32_ws: fp32 workspace >= splitk * M * N (per-slice partials —
-  // no zeroing, no atomics); residual (optional [M, N] bf16) is folded
-  // into the combine kernel.
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1);
-  TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1);
-  int M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M <= 16 && K % 32 == 0 && N % SG_TN == 0);
-  TORCH_CHECK(x.stride(0) == K, "x must be contiguous");
-  int kslice = (K / (int)splitk + 63) / 64 * 64;
-  int nks = (K + kslice - 1) / kslice;
-  TORCH_CHECK(out32_ws.numel() >= (long)nks * M * N, "workspace too small");
-  auto out32 = out32_ws.narrow(0, 0, (long)nks * M * N);
-  size_t lds = (size_t)16 * kslice * sizeof(short);
-  TORCH_CHECK(lds <= 160 * 1024, "kslice too large for LDS");
-  auto launch = [&](auto nb, auto wvs) {
-    dim3 grid(N / (16 * wvs.value), nks);
-    hipLaunchKernelGGL((skinny_gemm_kernel<nb.value, wvs.value>), grid,
-      dim3(64 * wvs.value), lds, cur_stream(),
-      (const bf16*)x.data_ptr(), (const bf16*)w.data_ptr(),
-      out32.data_ptr<float>(), M, N, K, kslice);
-  };
-  using c4 = std::integral_constant<int, 4>;
-  using c8 = std::integral_constant<int, 8>;
-  using c2 = std::integral_constant<int, 2>;
-  sg_dispatch(N, [&]{ launch(c4{}, c4{}); }, [&]{ launch(c8{}, c4{}); },
-              [&]{ launch(c4{}, c2{}); }, [&]{ launch(c8{}, c2{}); });
-  auto out = torch::empty({M, (long)N}, x.options());
-  long n = (long)M * N;
+  const SgShape s = sg_shape(x, w, out32_ws, splitk);
+  auto out32 = sg_partials(x, w, out32_ws, s);
+  auto out = torch::empty({s.M, (long)s.N}, x.options());
+  long n = (long)s.M * s.N;
   int cgrid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
-  const bf16* rptr = nullptr;
-  if (residual.has_value()) {
-    TORCH_CHECK(residual->is_contiguous() && residual->numel() == n);
-    rptr = (const bf16*)residual->data_ptr();
-  }
+  const bf16* rptr = sg_resid_ptr(residual, n);
   hipLaunchKernelGGL(sg_combine_kernel, dim3(cgrid), dim3(256), 0,
     cur_stream(), out32.data_ptr<float>(), rptr, (bf16*)out.data_ptr(), n,
-    nks);
+    s.nks);
   CHECK_CUDA_OK();
   return out;
 }

@@ -157,6 +157,84 @@ def test_attn_varlen_fwd(nq, nkv, lens):
     assert torch.isfinite(lse[:, 0]).all()
 
 
+def test_attn_varlen_fwd_hd64():
+    """The <64> instantiation of the single-buffer forward (models launch it;
+    the hd=128 cases above do not)."""
+    torch.manual_seed(6)
+    nq, nkv, hd, lens = 8, 8, 64, [1, 17, 330]
+    total = sum(lens)
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device="cuda")
+    q = torch.randn(total, nq, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    k = torch.randn(total, nkv, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    v = torch.randn(total, nkv, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    scale = 1.0 / np.sqrt(hd)
+    out, lse = C.attn_varlen_fwd(q, k, v, cu, max(lens), True, scale, 0)
+    ref = F.attn_varlen_ref(
+        q.float().cpu(), k.float().cpu(), v.float().cpu(), cu.cpu(), True, scale
+    )
+    torch.testing.assert_close(out.float().cpu(), ref, atol=3e-2, rtol=3e-2)
+    assert torch.isfinite(lse[:, 0]).all()
+
+
+# Runs in a fresh interpreter: the extension reads REALHF_AMD_ATTN_DB once per
+# process.  Case 1: L=1, a sequence inside one tile, and three query blocks
+# with six KV tiles (both ping-pong buffers reused, last tile 10 keys).
+# Case 2: sliding window with kv_begin > 0 in the second query block and a
+# KV-tile count of 1 and of 2.
+_ATTN_DB_CHILD = r"""
+import faulthandler
+faulthandler.dump_traceback_later(100, exit=True)
+import numpy as np
+import torch
+from realhf_amd.ops import functional as F
+import realhf_amd._C as C
+
+cases = [
+    (128, 8, 2, [1, 17, 330], 0, 3e-2),
+    (64, 8, 8, [130, 64], 48, 0.05),
+]
+for hd, nq, nkv, lens, window, atol in cases:
+    torch.manual_seed(31)
+    total = sum(lens)
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device="cuda")
+    q = torch.randn(total, nq, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    k = torch.randn(total, nkv, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    v = torch.randn(total, nkv, hd, dtype=torch.bfloat16, device="cuda") * 0.5
+    scale = 1.0 / np.sqrt(hd)
+    out, lse = C.attn_varlen_fwd(q, k, v, cu, max(lens), True, scale, window)
+    qf, kf, vf = q.float().cpu(), k.float().cpu(), v.float().cpu()
+    ref = F.attn_varlen_ref(qf, kf, vf, cu.cpu(), True, scale,
+                            window=window if window > 0 else None)
+    err = (out.float().cpu() - ref).abs().max().item()
+    print("hd", hd, "window", window, "max |out - ref|", err, flush=True)
+    torch.testing.assert_close(out.float().cpu(), ref, atol=atol, rtol=3e-2)
+    # row 0 of a sequence sees key 0 only: lse = logsumexp of that one score
+    rep = nq // nkv
+    for s in cu[:-1].tolist():
+        scores = (qf[s] * kf[s].repeat_interleave(rep, dim=0)).sum(-1, keepdim=True) * scale
+        want = torch.logsumexp(scores, dim=-1)
+        lerr = (lse[s].cpu() - want).abs().max().item()
+        print("  seq start", s, "max |lse - ref|", lerr, flush=True)
+        assert lerr <= 1e-2, (s, lerr)
+"""
+
+
+def test_attn_varlen_fwd_double_buffered():
+    """REALHF_AMD_ATTN_DB=1: the double-buffered forward vs the fp32 oracle,
+    at the tolerances of the single-buffer tests."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else [])
+    r = subprocess.run(
+        cmd + ["-c", _ATTN_DB_CHILD], cwd=root, timeout=120,
+        env=dict(os.environ, REALHF_AMD_ATTN_DB="1"),
+        capture_output=True, text=True,
+    )
+    assert r.returncode == 0, f"stdout:\n{r.stdout}\nstderr:\n{r.stderr}"
+
+
 @pytest.mark.parametrize("nq,nkv,hd", [(32, 32, 128), (8, 2, 128), (8, 8, 64)])
 def test_attn_decode(nq, nkv, hd):
     torch.manual_seed(7)

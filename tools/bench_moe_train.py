@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """MoE (Mixtral-style) TRAINING microbench — evidence that the GRPO
 Mixtral path trains on the hand-written MFMA grouped-GEMM kernels
-(fwd: ops/csrc/grouped_gemm.hip, bwd dX/dW: grouped_gemm_bwd.hip).
+(fwd and bwd dX/dW: ops/csrc/grouped_gemm.hip).
 
 Run under rocprofv3 --stats to see grouped_gemm_kernel /
 grouped_gemm_dx_kernel / grouped_gemm_dw_kernel among the top entries:
