@@ -64,6 +64,13 @@ torch::Tensor rope_qkv_decode(
     torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
     torch::Tensor vcache, torch::Tensor cache_seqlens, torch::Tensor cosb,
     torch::Tensor sinb, long nq, bool apply_rope);
+std::vector<torch::Tensor> vocab_logprob_fwd(torch::Tensor logits,
+                                             torch::Tensor labels,
+                                             long vocab_start,
+                                             long ignore_index);
+torch::Tensor vocab_logprob_bwd(torch::Tensor logits, torch::Tensor labels,
+                                torch::Tensor lse, torch::Tensor grad_out,
+                                long vocab_start, long ignore_index);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -98,4 +105,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xgmi_status", &xgmi_status);
   m.def("xgmi_destroy", &xgmi_destroy);
   m.def("mcmc_search", &mcmc_search);
+  m.def("vocab_logprob_fwd", &vocab_logprob_fwd);
+  m.def("vocab_logprob_bwd", &vocab_logprob_bwd);
 }

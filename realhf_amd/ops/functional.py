@@ -11,6 +11,8 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
   slice_intervals /
   set_intervals      — flat-param interval gather/scatter (realhf._C.interval_op_cuda)
   fused_adamw        — flat-buffer AdamW (reference: apex fused adam via Megatron)
+  vocab_logprobs     — per-token log-prob over a vocab slice, fwd/bwd without
+                       fp32 [tokens, vocab] temporaries (opt-in, see parallel/tp.py)
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -462,6 +464,121 @@ def gae(rewards, values, cu_seqlens, bootstrap, gamma, lam):
         C = _ops.require_hip()
         return C.gae_1d(rewards, values, cu_seqlens, bootstrap, float(gamma), float(lam))
     return gae_ref(rewards, values, cu_seqlens, bootstrap, gamma, lam)
+
+
+# ---------------------------------------------------------------------------
+# Vocab log-probs: per-row (target logit, max, sum-exp) over a vocab slice
+# ---------------------------------------------------------------------------
+def vocab_logprob_stats_ref(
+    logits: torch.Tensor,  # [n, v_local]
+    labels: torch.Tensor,  # [n] int64 global vocab ids
+    vocab_start: int = 0,
+    ignore_index: int = -100,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(target, rowmax, sumexp), all fp32 [n], over the local vocab slice:
+    rowmax = max_j x, sumexp = sum_j exp(x - rowmax), target = the raw logit
+    at column label - vocab_start if that lies in the slice, else 0.  An
+    all -inf slice gives (rowmax, sumexp) = (-inf, 0); ignored rows give
+    (0, 0, 1)."""
+    x = logits.float()
+    v_local = x.shape[-1]
+    rowmax = x.max(dim=-1).values
+    finite_max = torch.where(torch.isinf(rowmax) & (rowmax < 0),
+                             torch.zeros_like(rowmax), rowmax)
+    sumexp = (x - finite_max.unsqueeze(-1)).exp().sum(dim=-1)
+    local = labels - vocab_start
+    in_range = (local >= 0) & (local < v_local)
+    safe = local.clamp(0, v_local - 1)
+    target = x.gather(-1, safe.unsqueeze(-1)).squeeze(-1)
+    target = torch.where(in_range, target, torch.zeros_like(target))
+    ign = labels == ignore_index
+    target = target.masked_fill(ign, 0.0)
+    rowmax = rowmax.masked_fill(ign, 0.0)
+    sumexp = sumexp.masked_fill(ign, 1.0)
+    return target, rowmax, sumexp
+
+
+def vocab_logprob_bwd_ref(logits, labels, lse, grad_out, vocab_start=0,
+                          ignore_index=-100):
+    """dlogits = grad_out * (onehot(label - vocab_start) - exp(x - lse)) in
+    fp32, cast to logits.dtype; ignored rows are zero."""
+    v_local = logits.shape[-1]
+    g = (logits.float() - lse.unsqueeze(-1)).exp_().mul_(-grad_out.unsqueeze(-1))
+    local = labels - vocab_start
+    in_range = (local >= 0) & (local < v_local) & (labels != ignore_index)
+    safe = local.clamp(0, v_local - 1)
+    add = torch.where(in_range, grad_out, torch.zeros_like(grad_out))
+    g.scatter_add_(-1, safe.unsqueeze(-1), add.unsqueeze(-1))
+    g.masked_fill_((labels == ignore_index).unsqueeze(-1), 0.0)
+    return g.to(logits.dtype)
+
+
+def combine_vocab_stats(target, rowmax, sumexp, group=None):
+    """Merge per-slice statistics into (logp, lse).  group=None is the
+    single-rank case; with a group, three [n]-vector all-reduces (max, sum,
+    sum) merge the TP ranks' vocab slices."""
+    import torch.distributed as dist
+
+    g = rowmax.clone()
+    if group is not None:
+        dist.all_reduce(g, op=dist.ReduceOp.MAX, group=group)
+    # an all -inf slice has sumexp == 0 and possibly rowmax == g == -inf
+    factor = torch.where(sumexp == 0, torch.zeros_like(sumexp),
+                         (rowmax - g).exp())
+    se = sumexp * factor
+    t = target.clone()
+    if group is not None:
+        dist.all_reduce(se, group=group)
+        dist.all_reduce(t, group=group)
+    lse = g + se.log()
+    return t - lse, lse
+
+
+def _vocab_logprob_hip(logits: torch.Tensor) -> bool:
+    return _ops.use_hip(logits) and logits.dtype in (torch.bfloat16,
+                                                      torch.float32)
+
+
+class _VocabLogProbFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, vocab_start, group, ignore_index):
+        if _vocab_logprob_hip(logits):
+            C = _ops.require_hip()
+            logits = logits.contiguous()
+            labels = labels.contiguous()
+            stats = C.vocab_logprob_fwd(logits, labels, vocab_start,
+                                        ignore_index)
+        else:
+            stats = vocab_logprob_stats_ref(logits, labels, vocab_start,
+                                            ignore_index)
+        logp, lse = combine_vocab_stats(*stats, group=group)
+        logp = logp.masked_fill(labels == ignore_index, 0.0)
+        ctx.save_for_backward(logits, labels, lse)
+        ctx.vocab_start, ctx.ignore_index = vocab_start, ignore_index
+        return logp
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        logits, labels, lse = ctx.saved_tensors
+        grad_out = grad_out.float().contiguous()
+        if _vocab_logprob_hip(logits):
+            C = _ops.require_hip()
+            dlogits = C.vocab_logprob_bwd(logits, labels, lse, grad_out,
+                                          ctx.vocab_start, ctx.ignore_index)
+        else:
+            dlogits = vocab_logprob_bwd_ref(logits, labels, lse, grad_out,
+                                            ctx.vocab_start, ctx.ignore_index)
+        return dlogits, None, None, None, None
+
+
+def vocab_logprobs(logits, labels, *, vocab_start=0, group=None,
+                   ignore_index=-100):
+    """fp32 log p(label) per row of [n, v_local] logits whose columns are
+    the vocab slice starting at vocab_start; rows labelled ignore_index
+    give 0 and a zero gradient.  Saves only the logits, the labels and the
+    [n] log-sum-exp for backward."""
+    return _VocabLogProbFn.apply(logits, labels.long(), int(vocab_start), group,
+                                 int(ignore_index))
 
 
 # ---------------------------------------------------------------------------

@@ -5,7 +5,15 @@ Reference semantics: realhf/impl/model/parallelism/model_parallel/modules.py
 TP group; three small all-reduces (max, target-logit, sum-exp) replace
 gathering the [tokens, vocab] matrix (which at 32k vocab would be the
 largest activation in the step).
+
+REALHF_AMD_FUSED_LOGPROB=1 (opt-in, read at call time) routes bf16/fp32
+logits through ops.functional.vocab_logprobs instead: the same three
+all-reduces, but the per-rank statistics come from one HIP pass over the
+logits and backward recomputes the softmax from the saved logits, so no
+fp32 [tokens, v_local] tensor exists inside a rank either.
 """
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -54,8 +62,29 @@ class _VocabParallelLogProbs(torch.autograd.Function):
         return g, None
 
 
+IGNORE_INDEX = -100
+
+
+def _use_fused(logits: torch.Tensor) -> bool:
+    return (
+        os.environ.get("REALHF_AMD_FUSED_LOGPROB") == "1"
+        and logits.dtype in (torch.bfloat16, torch.float32)
+    )
+
+
 def vocab_parallel_logprobs(logits: torch.Tensor, labels: torch.Tensor):
     """log p(label) per row, with logits vocab-partitioned over TP."""
+    if _use_fused(logits):
+        from realhf_amd.ops import functional as F
+
+        tp = constants.tp_world_size() if constants.has_current() else 1
+        return F.vocab_logprobs(
+            logits,
+            labels,
+            vocab_start=(constants.tp_rank() if tp > 1 else 0) * logits.shape[-1],
+            group=constants.tp_group() if tp > 1 else None,
+            ignore_index=IGNORE_INDEX,
+        )
     return _VocabParallelLogProbs.apply(logits, labels)
 
 
@@ -72,4 +101,10 @@ def packed_shifted_logprobs(
     total = packed_input_ids.shape[0]
     leave = build_leave_one_indices(total, cu_seqlens)
     shift = build_shift_one_indices(total, cu_seqlens)
+    if _use_fused(logits):
+        # no logits[leave] copy: every row runs, the last token of each
+        # sequence is labelled ignore_index (logits not read, zero gradient)
+        labels = packed_input_ids.new_full((total,), IGNORE_INDEX)
+        labels[leave] = packed_input_ids[shift]
+        return vocab_parallel_logprobs(logits, labels)[leave]
     return vocab_parallel_logprobs(logits[leave], packed_input_ids[shift])

@@ -26,6 +26,7 @@ SRC = [
     "realhf_amd/ops/csrc/attn_varlen.hip",
     "realhf_amd/ops/csrc/all_reduce.hip",
     "realhf_amd/ops/csrc/attn_bwd.hip",
+    "realhf_amd/ops/csrc/logprob.hip",
 ]
 
 setup(
