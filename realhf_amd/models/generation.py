@@ -24,6 +24,7 @@ import torch
 from realhf_amd.api.model import GenerationHyperparameters
 from realhf_amd.base import logging
 from realhf_amd.models.real_model import ReaLModel
+from realhf_amd.ops import functional as ops
 from realhf_amd.utils.functional import top_k_top_p_logits  # noqa: F401 — re-exported for interface use
 
 logger = logging.getLogger("generate")
@@ -176,6 +177,17 @@ def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device):
     return s
 
 
+def decode_graph_supported(cfg, dtype, device) -> bool:
+    """Whether the dense decode step runs fully on HIP kernels, which is
+    what hipGraph capture needs: the torch fallback for other head dims or
+    dtypes reads cache_seqlens on the host."""
+    return (
+        torch.device(device).type == "cuda"
+        and dtype == torch.bfloat16
+        and cfg.head_dim in ops.HIP_ATTN_HEAD_DIMS
+    )
+
+
 @torch.no_grad()
 def generate(
     model: ReaLModel,
@@ -235,13 +247,10 @@ def generate(
     cache_seqlens = prompt_lens.to(torch.int32).clone()
 
     decoder = sess.decoder
-    # graph capture requires the fully HIP decode path (the torch
-    # fallback for odd head dims reads tensors on the host)
+    # graph capture requires the fully HIP decode path
     use_graph = (
         gconfig.use_hip_graph
-        and device.type == "cuda"
-        and model.dtype == torch.bfloat16
-        and cfg.head_dim in (64, 128)
+        and decode_graph_supported(cfg, model.dtype, device)
         # MoE dispatch reads expert counts on the host (counts.cpu());
         # a D2H sync inside stream capture DEADLOCKS rather than erroring.
         # pad_to_capacity makes counts compile-time constants (no sync) —

@@ -214,7 +214,7 @@ class ReaLModelBlock(nn.Module):
             and h.is_cuda
             and h.dtype == torch.bfloat16
             and not cfg.qk_layernorm
-            and self.hd in (64, 128)
+            and self.hd in ops.HIP_ATTN_HEAD_DIMS
             and _os.environ.get("REALHF_AMD_NO_FUSED_DECODE") != "1"
             and not self.lora  # adapters applied in the standard path
         ):

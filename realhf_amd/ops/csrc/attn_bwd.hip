@@ -82,8 +82,12 @@ __global__ void bw_reduce_dq(const float* __restrict__ part,
   ((f32x4*)dq)[idx] = acc + ((const f32x4*)dq)[idx];
 }
 
+// HD = 256 (gemma): the dK/dV accumulators alone are 128 registers per lane
+// and the tiles take 112 KB of LDS, so that instantiation asks for one
+// workgroup per CU; 64/128 keep two.
 template <int HD, bool DET>
-__global__ __launch_bounds__(64 * BW_WAVES, 2) void attn_varlen_bwd_kernel(
+__global__ __launch_bounds__(64 * BW_WAVES, HD > 128 ? 1 : 2)
+void attn_varlen_bwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const bf16* __restrict__ dout,
     const float* __restrict__ lse, const float* __restrict__ Dsum,
@@ -307,7 +311,8 @@ std::vector<torch::Tensor> attn_varlen_bwd(
   auto dk32 = torch::empty({(long)total, (long)nq, (long)hd}, f32);
   auto dv32 = torch::empty({(long)total, (long)nq, (long)hd}, f32);
   dim3 grid((unsigned)(total / BW_KV + bs), nq);
-  TORCH_CHECK(hd == 128 || hd == 64, "attn_varlen_bwd: hd 64/128 only");
+  TORCH_CHECK(hd == 256 || hd == 128 || hd == 64,
+              "attn_varlen_bwd: unsupported head_dim ", hd);
 #define BW_LAUNCH(HD_, DET_)                                              \
   hipLaunchKernelGGL((attn_varlen_bwd_kernel<HD_, DET_>), grid,           \
     dim3(64 * BW_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
@@ -318,7 +323,9 @@ std::vector<torch::Tensor> attn_varlen_bwd(
     dq32.data_ptr<float>(), dk32.data_ptr<float>(), dv32.data_ptr<float>(), \
     nq, nkv, (float)scale, causal, (int)window,                           \
     part_ptr, (int)nslot, part_stride)
-  if (hd == 128) {
+  if (hd == 256) {
+    if (det) BW_LAUNCH(256, true); else BW_LAUNCH(256, false);
+  } else if (hd == 128) {
     if (det) BW_LAUNCH(128, true); else BW_LAUNCH(128, false);
   } else {
     if (det) BW_LAUNCH(64, true); else BW_LAUNCH(64, false);
@@ -327,7 +334,12 @@ std::vector<torch::Tensor> attn_varlen_bwd(
   if (det) {
     const long n4 = part_stride / 4;
     dim3 rgrid((unsigned)((n4 + 255) / 256));
-    if (hd == 128) {
+    if (hd == 256) {
+      hipLaunchKernelGGL((bw_reduce_dq<256>), rgrid, dim3(256), 0,
+        cur_stream(), part_ptr, dq32.data_ptr<float>(),
+        cu_dev.data_ptr<int>(), bs, total, nq, (int)nslot, causal,
+        (int)window);
+    } else if (hd == 128) {
       hipLaunchKernelGGL((bw_reduce_dq<128>), rgrid, dim3(256), 0,
         cur_stream(), part_ptr, dq32.data_ptr<float>(),
         cu_dev.data_ptr<int>(), bs, total, nq, (int)nslot, causal,

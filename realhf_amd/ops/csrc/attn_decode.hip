@@ -24,6 +24,12 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2q;
 // nothing co-resident to overlap with), W=4 needs 64 KB (TWO WGs per CU:
 // one streams KV while the other runs its softmax/PV phase).  Default 4;
 // REALHF_AMD_DEC_WAVES ∈ {2,4,8} for A/B.
+// At HD=256 (gemma) the tile doubles: W=2 is 64 KB, W=4 is 128 KB and W=8
+// would be 256 KB, more than the 160 KB LDS — it is not instantiated, and
+// a request for 8 waves runs with 4.  The default stays 4 there: measured
+// against W=2 at bs 16 it is 10-20% faster at rep=1 and 43% faster at rep=8
+// with 8k keys, 6% slower only at rep=8 with 640 keys (docs/perf.md), i.e.
+// the deeper per-workgroup KV stream beats the second co-resident workgroup.
 // Split-K over the key range (flash-decoding): at decode batch sizes
 // bs*nkv < 256 a one-WG-per-(batch, kv-head) grid leaves most of the
 // 256 CUs idle; gridDim.y splits each sequence's keys into `nsplit`
@@ -37,7 +43,7 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
     const bf16* __restrict__ vc, const int* __restrict__ cache_seqlens,
     bf16* __restrict__ out, float* __restrict__ ws, int bs, int nq, int nkv,
     long maxlen, float scale, int window) {
-  constexpr int DPL = HD / WAVE;  // dims per lane (2 for hd=128)
+  constexpr int DPL = HD / WAVE;  // dims per lane (2 for hd=128, 4 for 256)
   const int b = blockIdx.x / nkv;
   const int kvh = blockIdx.x % nkv;
   const int nsplit = gridDim.y;
@@ -137,6 +143,13 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
           unsigned u = *(const unsigned*)(&v_s[w][j][lane * 2]);
           acc_w[r][0] += pj * bf2f((short)(u & 0xffff));
           acc_w[r][1] += pj * bf2f((short)(u >> 16));
+        } else if constexpr (DPL == 4) {
+          // hd=256: one b64 LDS read for the lane's four dims
+          uint2 u = *(const uint2*)(&v_s[w][j][lane * 4]);
+          acc_w[r][0] += pj * bf2f((short)(u.x & 0xffff));
+          acc_w[r][1] += pj * bf2f((short)(u.x >> 16));
+          acc_w[r][2] += pj * bf2f((short)(u.y & 0xffff));
+          acc_w[r][3] += pj * bf2f((short)(u.y >> 16));
         } else {
           #pragma unroll
           for (int d = 0; d < DPL; d++)
@@ -224,11 +237,13 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   int rep = nq / nkv;
   auto cs = cache_seqlens.to(torch::kInt);
   auto out = torch::empty_like(q);
-  static int dec_waves = [] {
+  static int dec_waves_env = [] {
     const char* e = getenv("REALHF_AMD_DEC_WAVES");
     int v = e ? atoi(e) : 4;
     return (v == 2 || v == 4 || v == 8) ? v : 4;
   }();
+  // W=8 at hd=256 would need 256 KB of LDS: run it with 4
+  const int dec_waves = (hd == 256 && dec_waves_env == 8) ? 4 : dec_waves_env;
   // split-K factor: fill the 256-CU chip when bs*nkv is small (decode
   // batches).  Static per shape -> hipGraph-safe; REALHF_AMD_DEC_SPLIT
   // overrides for A/B.
@@ -255,7 +270,11 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
         cs.data_ptr<int>(), (bf16*)out.data_ptr(), ws_ptr, bs, nq, nkv, maxlen,
         (float)scale, (int)window);
       if (ws_ptr) {
-        if (hd_c.value == 128)
+        if (hd_c.value == 256)
+          hipLaunchKernelGGL((attn_decode_combine_kernel<256>),
+            dim3((unsigned)(bs * nq)), dim3(WAVE), 0, cur_stream(),
+            ws_ptr, (bf16*)out.data_ptr(), nsplit);
+        else if (hd_c.value == 128)
           hipLaunchKernelGGL((attn_decode_combine_kernel<128>),
             dim3((unsigned)(bs * nq)), dim3(WAVE), 0, cur_stream(),
             ws_ptr, (bf16*)out.data_ptr(), nsplit);
@@ -266,7 +285,11 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
       }
     };
     if (dec_waves == 2) go(std::integral_constant<int, 2>{});
-    else if (dec_waves == 8) go(std::integral_constant<int, 8>{});
+    else if (dec_waves == 8) {
+      // never reached at hd=256 (clamped above); not instantiated there
+      if constexpr (decltype(hd_c)::value != 256)
+        go(std::integral_constant<int, 8>{});
+    }
     else go(std::integral_constant<int, 4>{});
   };
   #define REP_SWITCH(HDV) \
@@ -277,7 +300,8 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
       case 8: launch(std::integral_constant<int, HDV>{}, std::integral_constant<int, 8>{}); break; \
       default: TORCH_CHECK(false, "unsupported GQA ratio ", rep); \
     }
-  if (hd == 128) { REP_SWITCH(128) }
+  if (hd == 256) { REP_SWITCH(256) }
+  else if (hd == 128) { REP_SWITCH(128) }
   else if (hd == 64) { REP_SWITCH(64) }
   else { TORCH_CHECK(false, "unsupported head_dim ", hd); }
   #undef REP_SWITCH

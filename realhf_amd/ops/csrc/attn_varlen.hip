@@ -21,7 +21,6 @@
 #define AV_WAVES 8
 #define QW 16        // queries per wave
 #define KVBLK 64     // keys per LDS tile
-#define HDMAX 128
 #define KPAD 8       // K tile row pad (bf16 elems)
 #define VPAD 8       // P tile row pad
 // V stays ROW-major: the PV B-fragment is gathered by the hardware
@@ -48,6 +47,11 @@
 // larger LDS hurt more than the saved barrier+overlap help.  Kept behind
 // REALHF_AMD_ATTN_DB=1 as the baseline for future pipelining work;
 // default always uses the single-buffer scheme.
+//
+// HD = 256 (gemma) is instantiated for DB = false only: 85 KB of LDS
+// (K 33 KB + V 34 KB + P 18 KB), 64 accumulator VGPRs per lane.  Two KV
+// buffers plus P would be ~156 KB of the 160 KB LDS, so REALHF_AMD_ATTN_DB
+// is ignored at 256.
 template <int HD, bool DB>
 __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
@@ -298,7 +302,7 @@ std::vector<torch::Tensor> attn_varlen_fwd(
   dim3 grid((unsigned)(total / QBLK + bs), nq);
   int dbm = attn_db_mode();
   bool use_db = (dbm == 1) || (dbm == -1 && max_seqlen >= 4096);
-  TORCH_CHECK(hd == 128 || hd == 64, "unsupported head_dim ", hd);
+  TORCH_CHECK(hd == 256 || hd == 128 || hd == 64, "unsupported head_dim ", hd);
 #define FW_LAUNCH(HD_, DB_)                                               \
   hipLaunchKernelGGL((attn_varlen_fwd_kernel<HD_, DB_>), grid,            \
     dim3(64 * AV_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
@@ -306,7 +310,9 @@ std::vector<torch::Tensor> attn_varlen_fwd(
     cu_dev.data_ptr<int>(), blk_off.data_ptr<int>(), bs,                  \
     (bf16*)out.data_ptr(), lse.data_ptr<float>(), nq, nkv, (float)scale,  \
     causal, (int)window)
-  if (hd == 128) {
+  if (hd == 256) {
+    FW_LAUNCH(256, false);  // single-buffer only (LDS), whatever ATTN_DB says
+  } else if (hd == 128) {
     if (use_db) FW_LAUNCH(128, true); else FW_LAUNCH(128, false);
   } else {
     if (use_db) FW_LAUNCH(64, true); else FW_LAUNCH(64, false);

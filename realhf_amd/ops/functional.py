@@ -24,6 +24,12 @@ import torch
 
 from realhf_amd import ops as _ops
 
+# Head dims the HIP attention kernels (attn_varlen fwd/bwd, attn_decode) are
+# instantiated for.  The one gate for every caller: the varlen/decode
+# dispatch below, the fused decode epilogue (models/layers.py) and hipGraph
+# decode (models/generation.py, parallel/pp.py).
+HIP_ATTN_HEAD_DIMS = (64, 128, 256)
+
 
 # ---------------------------------------------------------------------------
 # RMSNorm
@@ -361,7 +367,7 @@ def attn_varlen(q, k, v, cu_seqlens, max_seqlen, causal=True, softmax_scale=None
     if (
         _ops.use_hip(q)
         and q.dtype == torch.bfloat16
-        and q.shape[-1] in (64, 128)
+        and q.shape[-1] in HIP_ATTN_HEAD_DIMS
         and (window is None or causal)
     ):
         return _AttnVarlenFn.apply(
@@ -415,7 +421,7 @@ def attn_decode(q, k_cache, v_cache, cache_seqlens, softmax_scale=None,
     if (
         _ops.use_hip(q)
         and q.dtype == torch.bfloat16
-        and q.shape[-1] in (64, 128)
+        and q.shape[-1] in HIP_ATTN_HEAD_DIMS
         and q.shape[1] // k_cache.shape[2] in (1, 2, 4, 8)
     ):
         C = _ops.require_hip()

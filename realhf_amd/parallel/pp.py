@@ -358,8 +358,8 @@ class PipelinedEngine(PipelinableEngine):
             st.append(s)
 
         use_graph = (
-            gconfig.use_hip_graph and dev.type == "cuda"
-            and dtype == torch.bfloat16 and cfg.head_dim in (64, 128)
+            gconfig.use_hip_graph
+            and genmod.decode_graph_supported(cfg, dtype, dev)
             and cfg.moe is None  # MoE counts.cpu() deadlocks under capture
         )
 
