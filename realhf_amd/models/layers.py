@@ -11,8 +11,9 @@ weights.  TP behavior comes from the current model scope's grid
 so the same code runs single-process on CPU.
 
 MI355X specifics: wq/wk/wv (and gate/up) flat regions are adjacent, so the
-module runs ONE hipBLASLt GEMM over the concatenated view; RMSNorm / RoPE /
-SwiGLU / attention are the hand-written HIP kernels in realhf_amd.ops.
+module runs ONE hipBLASLt GEMM over the concatenated view; RMSNorm (plain
+and gemma's 1 + w) / RoPE / SwiGLU / GeGLU / attention are the hand-written
+HIP kernels in realhf_amd.ops.
 """
 import math
 from typing import Dict, Optional
@@ -254,17 +255,24 @@ class ReaLModelBlock(nn.Module):
                                        scale, window=cfg.sliding_window)
             attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
             wo = self.p[f"{i}.attn.wo.weight"]
+            # fused (x + o) + mlp-norm: plain RMS, or gemma's 1 + w mode
+            add_norm = None
+            if self.moe is not None:
+                pass
+            elif cfg.norm_type == "rms":
+                add_norm = C.add_rmsnorm_fwd
+            elif cfg.norm_type == "gemma_rms" and ops.gemma_ops_enabled():
+                add_norm = C.gemma_add_rmsnorm_fwd
             if (
                 self.tp_size == 1
                 and f"{i}.attn.wo.bias" not in self.p
-                and cfg.norm_type == "rms"
-                and self.moe is None
+                and add_norm is not None
             ):
                 # launch-boundary reduce: o's split-K slabs are summed in
                 # the fused add+rmsnorm prologue (no combine, no bf16 o)
                 o_parts = ops.skinny_linear_nc(attn_out, wo)
                 if o_parts is not None:
-                    h2, x2 = C.add_rmsnorm_fwd(
+                    h2, x2 = add_norm(
                         o_parts, x, self.p[f"{i}.mlp.ln.weight"],
                         cfg.layer_norm_epsilon,
                     )
@@ -275,10 +283,10 @@ class ReaLModelBlock(nn.Module):
             o = mappings.reduce_from_tp_region(o)
             if f"{i}.attn.wo.bias" in self.p:
                 o = o + self.p[f"{i}.attn.wo.bias"]
-            if cfg.norm_type == "rms" and self.moe is None:
+            if add_norm is not None:
                 # fused (x + o) + mlp-norm, then the MLP body (the down
                 # projection folds the x2 residual into its combine)
-                h2, x2 = C.add_rmsnorm_fwd(
+                h2, x2 = add_norm(
                     o, x, self.p[f"{i}.mlp.ln.weight"], cfg.layer_norm_epsilon
                 )
                 return self._mlp_body(h2, sp, residual=x2)
@@ -416,13 +424,17 @@ class ReaLModelBlock(nn.Module):
             if fused_col:
                 gu = mappings.column_parallel_linear(h, merged, sp)
             elif merged is not None:
-                if cfg.activation == "silu" and self.tp_size == 1:
-                    # launch-boundary reduce: slabs summed in swiglu
+                if self.tp_size == 1 and (
+                    cfg.activation == "silu" or ops.gemma_ops_enabled()
+                ):
+                    # launch-boundary reduce: slabs summed in swiglu/geglu
                     gu_parts = ops.skinny_linear_nc(h, merged)
                     if gu_parts is not None:
                         from realhf_amd import ops as _ops_pkg
 
-                        act = _ops_pkg.require_hip().swiglu_fwd(gu_parts)
+                        C = _ops_pkg.require_hip()
+                        act = (C.swiglu_fwd if cfg.activation == "silu"
+                               else C.geglu_fwd)(gu_parts)
                 if act is None:
                     gu = ops.maybe_skinny_linear(h, merged)
                     if gu is None:
@@ -436,10 +448,7 @@ class ReaLModelBlock(nn.Module):
             elif cfg.activation == "silu":
                 act = ops.swiglu(gu)
             else:  # geglu (gemma)
-                gate, up = gu.chunk(2, dim=-1)
-                act = (
-                    F.gelu(gate.float(), approximate="tanh") * up.float()
-                ).to(gu.dtype)
+                act = ops.geglu(gu)
         else:
             up = _linear(h, self.p[f"{i}.mlp.up.weight"], self.p.get(f"{i}.mlp.up.bias"))
             act = F.gelu(up, approximate="tanh")

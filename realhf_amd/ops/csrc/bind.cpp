@@ -7,10 +7,20 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor rstd);
 std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
                                            torch::Tensor w, double eps);
+// Gemma weight mode (scale by 1 + w, summed in fp32): same arguments
+std::vector<torch::Tensor> gemma_rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
+                                             double eps);
+std::vector<torch::Tensor> gemma_rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                             torch::Tensor w, torch::Tensor rstd);
+std::vector<torch::Tensor> gemma_add_rmsnorm_fwd(torch::Tensor x,
+                                                 torch::Tensor resid,
+                                                 torch::Tensor w, double eps);
 torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cosb, torch::Tensor sinb,
                        torch::Tensor positions, bool interleaved, bool conj);
 torch::Tensor swiglu_fwd(torch::Tensor gu);
 torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu);
+torch::Tensor geglu_fwd(torch::Tensor gu);
+torch::Tensor geglu_bwd(torch::Tensor dy, torch::Tensor gu);
 std::vector<torch::Tensor> gae_1d(torch::Tensor rewards, torch::Tensor values,
                                   torch::Tensor cu_seqlens, torch::Tensor bootstrap,
                                   double gamma, double lam);
@@ -76,9 +86,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
+  m.def("gemma_rmsnorm_fwd", &gemma_rmsnorm_fwd);
+  m.def("gemma_rmsnorm_bwd", &gemma_rmsnorm_bwd);
+  m.def("gemma_add_rmsnorm_fwd", &gemma_add_rmsnorm_fwd);
   m.def("rope_fwd", &rope_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("geglu_fwd", &geglu_fwd);
+  m.def("geglu_bwd", &geglu_bwd);
   m.def("gae_1d", &gae_1d);
   m.def("slice_intervals", &slice_intervals);
   m.def("set_intervals", &set_intervals);

@@ -1,4 +1,4 @@
-// RoPE + SwiGLU + fused AdamW — memory-bound elementwise kernels for gfx950.
+// RoPE + SwiGLU/GeGLU + fused AdamW — memory-bound elementwise kernels for gfx950.
 // All bf16/f16 I/O is 8-element vectorized (guide G13); trig tables are
 // host-precomputed (guide Appendix B: no sinf/cosf on device).
 #include "common.h"
@@ -74,9 +74,23 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cosb, torch::Tensor sinb,
 }
 
 // ---------------------------------------------------------------------------
-// SwiGLU: gate_up [tokens, 2*I] -> out [tokens, I]; out = silu(g) * u
+// Gated MLP activation: gate_up [tokens, 2*I] -> out [tokens, I];
+// out = act(g) * u, with act = SiLU (SwiGLU) or tanh-GELU (GeGLU, GELU=true).
+// Both are g * sigmoid(a(g)): a = g for SiLU, and since
+// 0.5 * (1 + tanh z) = sigmoid(2z), a = 2z = 2*sqrt(2/pi) * (g + 0.044715 g^3)
+// for GELU — one __expf and one division either way, no tanhf.
+// Overflow: a -> -inf gives __expf(-a) = +inf and g / inf = -0; a -> +inf
+// gives g / 1 = g.
 // ---------------------------------------------------------------------------
-template <typename T>
+#define GELU_2C 1.5957691216057308f  // 2 * sqrt(2/pi)
+
+template <bool GELU>
+DEVINL float glu_sig_arg(float g) {
+  if constexpr (GELU) return GELU_2C * g * (1.f + 0.044715f * g * g);
+  else return g;
+}
+
+template <typename T, bool GELU = false>
 __global__ void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ out,
                                   long tokens, int I) {
   long n = tokens * (I / 8);
@@ -93,7 +107,7 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ out,
     for (int j = 0; j < 8; j++) {
       float gf = to_f32<T>(((const T*)&gv)[j]);
       float uf = to_f32<T>(((const T*)&uv)[j]);
-      float s = gf / (1.f + __expf(-gf));
+      float s = gf / (1.f + __expf(-glu_sig_arg<GELU>(gf)));
       ((T*)o)[j] = from_f32<T>(s * uf);
     }
     *(short8*)(out + t * (long)I + d0) = *(short8*)o;
@@ -102,7 +116,7 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ out,
 
 // slab variant: gate_up comes in as fp32 split-K partial slabs
 // [nks, tokens, 2I] from skinny_gemm_nc (launch-boundary reduce)
-template <typename T>
+template <typename T, bool GELU = false>
 __global__ void swiglu_slab_kernel(const float* __restrict__ parts, int nks,
                                    T* __restrict__ out, long tokens, int I) {
   const long sstride = tokens * (2L * I);
@@ -131,14 +145,17 @@ __global__ void swiglu_slab_kernel(const float* __restrict__ parts, int nks,
     short o[8];
     #pragma unroll
     for (int j = 0; j < 8; j++) {
-      float sg = gf[j] / (1.f + __expf(-gf[j]));
+      float sg = gf[j] / (1.f + __expf(-glu_sig_arg<GELU>(gf[j])));
       ((T*)o)[j] = from_f32<T>(sg * uf[j]);
     }
     *(short8*)(out + t * (long)I + d0) = *(short8*)o;
   }
 }
 
-template <typename T>
+// backward: d_up = dy * act(g); d_gate = dy * u * act'(g) with
+// act'(g) = sig + g * sig * (1 - sig) * a'(g), sig = sigmoid(a(g));
+// a' = 1 for SiLU, 2*sqrt(2/pi) * (1 + 0.134145 g^2) for GELU.
+template <typename T, bool GELU = false>
 __global__ void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ gu,
                                   T* __restrict__ dgu, long tokens, int I) {
   long n = tokens * (I / 8);
@@ -157,9 +174,17 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict_
       float gf = to_f32<T>(((const T*)&gv)[j]);
       float uf = to_f32<T>(((const T*)&uv)[j]);
       float d = to_f32<T>(((const T*)&dv)[j]);
-      float sig = 1.f / (1.f + __expf(-gf));
+      float sig = 1.f / (1.f + __expf(-glu_sig_arg<GELU>(gf)));
       float s = gf * sig;
-      ((T*)dg)[j] = from_f32<T>(d * uf * (sig + s * (1.f - sig)));
+      if constexpr (GELU) {
+        // in the saturated tails sig * (1 - sig) is exactly 0 and a' may be
+        // inf (g^2 overflows for |g| > 1.8e19): select, never 0 * inf
+        float tail = s * (1.f - sig);
+        float da = GELU_2C * (1.f + 0.134145f * gf * gf);
+        ((T*)dg)[j] = from_f32<T>(d * uf * (sig + (tail == 0.f ? 0.f : tail * da)));
+      } else {
+        ((T*)dg)[j] = from_f32<T>(d * uf * (sig + s * (1.f - sig)));
+      }
       ((T*)du)[j] = from_f32<T>(d * s);
     }
     *(short8*)(dgu + t * (2L * I) + d0) = *(short8*)dg;
@@ -167,8 +192,9 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dy, const T* __restrict_
   }
 }
 
-torch::Tensor swiglu_fwd(torch::Tensor gu) {
-  TORCH_CHECK(gu.is_contiguous());
+template <bool GELU>
+static torch::Tensor glu_fwd_impl(torch::Tensor gu) {
+  TORCH_CHECK(gu.is_cuda() && gu.is_contiguous());
   int I2 = gu.size(-1);
   TORCH_CHECK(I2 % 16 == 0);
   if (gu.dim() == 3 && gu.scalar_type() == torch::kFloat) {
@@ -179,7 +205,7 @@ torch::Tensor swiglu_fwd(torch::Tensor gu) {
                             gu.options().dtype(torch::kBFloat16));
     long n = tokens * (I / 8);
     int grid = (int)std::min<long>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL((swiglu_slab_kernel<bf16>), dim3(grid), dim3(256), 0,
+    hipLaunchKernelGGL((swiglu_slab_kernel<bf16, GELU>), dim3(grid), dim3(256), 0,
       cur_stream(), gu.data_ptr<float>(), (int)gu.size(0),
       (bf16*)out.data_ptr(), tokens, I);
     CHECK_CUDA_OK();
@@ -193,7 +219,7 @@ torch::Tensor swiglu_fwd(torch::Tensor gu) {
   int grid = (int)std::min<long>((n + 255) / 256, 8192);
   DISPATCH_BF16_FP16_FP32(gu.scalar_type(), "swiglu", [&] {
     if constexpr (sizeof(scalar_t) == 2)
-      hipLaunchKernelGGL((swiglu_fwd_kernel<scalar_t>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((swiglu_fwd_kernel<scalar_t, GELU>), dim3(grid), dim3(256), 0,
         cur_stream(), (const scalar_t*)gu.data_ptr(), (scalar_t*)out.data_ptr(),
         tokens, I);
   });
@@ -201,7 +227,8 @@ torch::Tensor swiglu_fwd(torch::Tensor gu) {
   return out;
 }
 
-torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu) {
+template <bool GELU>
+static torch::Tensor glu_bwd_impl(torch::Tensor dy, torch::Tensor gu) {
   int I2 = gu.size(-1);
   long tokens = gu.numel() / I2;
   int I = I2 / 2;
@@ -210,12 +237,21 @@ torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu) {
   int grid = (int)std::min<long>((n + 255) / 256, 8192);
   DISPATCH_BF16_FP16_FP32(gu.scalar_type(), "swiglu_bwd", [&] {
     if constexpr (sizeof(scalar_t) == 2)
-      hipLaunchKernelGGL((swiglu_bwd_kernel<scalar_t>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((swiglu_bwd_kernel<scalar_t, GELU>), dim3(grid), dim3(256), 0,
         cur_stream(), (const scalar_t*)dy.data_ptr(), (const scalar_t*)gu.data_ptr(),
         (scalar_t*)dgu.data_ptr(), tokens, I);
   });
   CHECK_CUDA_OK();
   return dgu;
+}
+
+torch::Tensor swiglu_fwd(torch::Tensor gu) { return glu_fwd_impl<false>(gu); }
+torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu) {
+  return glu_bwd_impl<false>(dy, gu);
+}
+torch::Tensor geglu_fwd(torch::Tensor gu) { return glu_fwd_impl<true>(gu); }
+torch::Tensor geglu_bwd(torch::Tensor dy, torch::Tensor gu) {
+  return glu_bwd_impl<true>(dy, gu);
 }
 
 // ---------------------------------------------------------------------------

@@ -2,9 +2,19 @@
 // HBM-bound: vectorized 16-byte loads (guide G13: scalar bf16 is 2x slower).
 // One 256-thread workgroup per row (hidden <= 16384), grid-stride over rows.
 // Replaces the reference's TransformerEngine RMSNorm (SURVEY.md §2.2 ext deps).
+//
+// Weight mode (compile-time, GEMMA): plain RMSNorm scales by w, Gemma by
+// 1 + w.  The sum is formed in fp32 from the stored weight, as HF Gemma and
+// gemma_rms_norm_ref do; in bf16 it would keep 8 mantissa bits of 1 + w.
 #include "common.h"
 
-template <typename T, int VEC, bool RESID = false>
+template <typename T, bool GEMMA>
+DEVINL float norm_weight(T w) {
+  if constexpr (GEMMA) return 1.0f + to_f32<T>(w);
+  else return to_f32<T>(w);
+}
+
+template <typename T, int VEC, bool RESID = false, bool GEMMA = false>
 __global__ void rmsnorm_fwd_kernel(
     const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out,
     float* __restrict__ rstd, int rows, int H, float eps,
@@ -48,7 +58,7 @@ __global__ void rmsnorm_fwd_kernel(
       *(float4v*)wv = *(const float4v*)(w + i);
       #pragma unroll
       for (int j = 0; j < VEC; j++)
-        o[j] = from_f32<T>(to_f32<T>(v[j]) * rs * to_f32<T>(wv[j]));
+        o[j] = from_f32<T>(to_f32<T>(v[j]) * rs * norm_weight<T, GEMMA>(wv[j]));
       *(float4v*)(yr + i) = *(float4v*)o;
     }
     __syncthreads();
@@ -58,7 +68,7 @@ __global__ void rmsnorm_fwd_kernel(
 // slab variant of the fused add+rmsnorm: x comes in as fp32 split-K
 // partial slabs [nks, rows, H] from skinny_gemm_nc (launch-boundary
 // reduce); sum_out = sum_s(parts) + resid, out = rmsnorm(sum_out).
-template <typename T, int VEC>
+template <typename T, int VEC, bool GEMMA = false>
 __global__ void add_rmsnorm_slab_kernel(
     const float* __restrict__ parts, int nks, const T* __restrict__ resid,
     const T* __restrict__ w, T* __restrict__ out, T* __restrict__ sum_out,
@@ -112,19 +122,22 @@ __global__ void add_rmsnorm_slab_kernel(
       *(float4v*)wv = *(const float4v*)(w + i);
       #pragma unroll
       for (int j = 0; j < VEC; j++)
-        o[j] = from_f32<T>(to_f32<T>(v[j]) * rs * to_f32<T>(wv[j]));
+        o[j] = from_f32<T>(to_f32<T>(v[j]) * rs * norm_weight<T, GEMMA>(wv[j]));
       *(float4v*)(yr + i) = *(float4v*)o;
     }
     __syncthreads();
   }
 }
 
-// backward: dx = rs * w * dy - rs^3/H * x * sum(dy * w * x)
-// dw: per-thread register partials over this block's rows (each thread owns
-// fixed columns), ONE atomicAdd per column per block at the end.
+// backward: dx = rs * w * dy - rs^3/H * x * sum(dy * w * x), with w the
+// effective weight (1 + w in Gemma mode); dw = sum_rows dy * x * rs in both.
+// dw: per-thread partials over this block's rows (each thread owns fixed
+// columns), written as ONE partial row per block at the end.
 #define RMS_MAX_COLS 64  // supports H <= 256 threads * VEC * (64/VEC)
-template <typename T, int VEC>
-__global__ void rmsnorm_bwd_kernel(
+#define RMS_THREADS 256
+
+template <typename T, int VEC, bool GEMMA = false>
+__global__ void __launch_bounds__(GEMMA ? RMS_THREADS : 1024) rmsnorm_bwd_kernel(
     const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ w,
     const float* __restrict__ rstd, T* __restrict__ dx,
     float* __restrict__ dw, int rows, int H) {
@@ -145,7 +158,7 @@ __global__ void rmsnorm_bwd_kernel(
       *(float4v*)c = *(const float4v*)(xr + i);
       #pragma unroll
       for (int j = 0; j < VEC; j++)
-        dot += to_f32<T>(a[j]) * to_f32<T>(b[j]) * to_f32<T>(c[j]);
+        dot += to_f32<T>(a[j]) * norm_weight<T, GEMMA>(b[j]) * to_f32<T>(c[j]);
     }
     dot = wave_sum(dot);
     int wid = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
@@ -158,35 +171,72 @@ __global__ void rmsnorm_bwd_kernel(
     }
     __syncthreads();
     float k = red[0] * rs * rs * rs / H;
-    int slot = 0;
-    for (int i = threadIdx.x * VEC; i < H; i += blockDim.x * VEC, slot += VEC) {
-      T a[VEC], b[VEC], c[VEC], o[VEC];
-      *(float4v*)a = *(const float4v*)(dyr + i);
-      *(float4v*)b = *(const float4v*)(w + i);
-      *(float4v*)c = *(const float4v*)(xr + i);
+    if constexpr (GEMMA) {
+      // the loop below with compile-time trips and slots (launched with
+      // RMS_THREADS threads): dwacc is indexed by constants only and stays
+      // in registers, where the runtime slot puts it in scratch
       #pragma unroll
-      for (int j = 0; j < VEC; j++) {
-        float g = to_f32<T>(a[j]);
-        float xv = to_f32<T>(c[j]);
-        o[j] = from_f32<T>(rs * to_f32<T>(b[j]) * g - k * xv);
-        if (slot + j < RMS_MAX_COLS) dwacc[slot + j] += g * xv * rs;
+      for (int c = 0; c < RMS_MAX_COLS / VEC; c++) {
+        int i = (c * RMS_THREADS + (int)threadIdx.x) * VEC;
+        if (i >= H) continue;
+        T a[VEC], b[VEC], cx[VEC], o[VEC];
+        *(float4v*)a = *(const float4v*)(dyr + i);
+        *(float4v*)b = *(const float4v*)(w + i);
+        *(float4v*)cx = *(const float4v*)(xr + i);
+        #pragma unroll
+        for (int j = 0; j < VEC; j++) {
+          float g = to_f32<T>(a[j]);
+          float xv = to_f32<T>(cx[j]);
+          o[j] = from_f32<T>(rs * norm_weight<T, true>(b[j]) * g - k * xv);
+          dwacc[c * VEC + j] += g * xv * rs;
+        }
+        *(float4v*)(dxr + i) = *(float4v*)o;
       }
-      *(float4v*)(dxr + i) = *(float4v*)o;
+    } else {
+      int slot = 0;
+      for (int i = threadIdx.x * VEC; i < H; i += blockDim.x * VEC, slot += VEC) {
+        T a[VEC], b[VEC], c[VEC], o[VEC];
+        *(float4v*)a = *(const float4v*)(dyr + i);
+        *(float4v*)b = *(const float4v*)(w + i);
+        *(float4v*)c = *(const float4v*)(xr + i);
+        #pragma unroll
+        for (int j = 0; j < VEC; j++) {
+          float g = to_f32<T>(a[j]);
+          float xv = to_f32<T>(c[j]);
+          o[j] = from_f32<T>(rs * to_f32<T>(b[j]) * g - k * xv);
+          if (slot + j < RMS_MAX_COLS) dwacc[slot + j] += g * xv * rs;
+        }
+        *(float4v*)(dxr + i) = *(float4v*)o;
+      }
     }
     __syncthreads();
   }
   // one partial row per block — no atomics (2048 blocks contending on
   // 4096 floats serialized ~500x; partials + torch sum is ~30x faster)
-  int slot = 0;
   float* dwrow = dw + (long)blockIdx.x * H;
-  for (int i = threadIdx.x * VEC; i < H; i += blockDim.x * VEC, slot += VEC) {
+  if constexpr (GEMMA) {
     #pragma unroll
-    for (int j = 0; j < VEC; j++)
-      if (slot + j < RMS_MAX_COLS) dwrow[i + j] = dwacc[slot + j];
+    for (int c = 0; c < RMS_MAX_COLS / VEC; c++) {
+      int i = (c * RMS_THREADS + (int)threadIdx.x) * VEC;
+      if (i >= H) continue;
+      #pragma unroll
+      for (int j = 0; j < VEC; j++) dwrow[i + j] = dwacc[c * VEC + j];
+    }
+  } else {
+    int slot = 0;
+    for (int i = threadIdx.x * VEC; i < H; i += blockDim.x * VEC, slot += VEC) {
+      #pragma unroll
+      for (int j = 0; j < VEC; j++)
+        if (slot + j < RMS_MAX_COLS) dwrow[i + j] = dwacc[slot + j];
+    }
   }
 }
 
-std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
+// Host side: one launcher per op, templated on the weight mode; the exported
+// rmsnorm_* functions are plain RMSNorm, the gemma_* ones the 1 + w mode.
+template <bool GEMMA>
+static std::vector<torch::Tensor> rmsnorm_fwd_impl(torch::Tensor x, torch::Tensor w,
+                                                   double eps) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous());
   int H = x.size(-1);
   long rows = x.numel() / H;
@@ -197,11 +247,11 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double 
   int grid = (int)std::min<long>(rows, 2048);
   DISPATCH_BF16_FP16_FP32(x.scalar_type(), "rmsnorm_fwd", [&] {
     if (x.element_size() == 2) {
-      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 8>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 8, false, GEMMA>), dim3(grid), dim3(256), 0,
         cur_stream(), (const scalar_t*)x.data_ptr(), (const scalar_t*)w.data_ptr(),
         (scalar_t*)out.data_ptr(), rstd.data_ptr<float>(), (int)rows, H, (float)eps);
     } else {
-      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 4>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 4, false, GEMMA>), dim3(grid), dim3(256), 0,
         cur_stream(), (const scalar_t*)x.data_ptr(), (const scalar_t*)w.data_ptr(),
         (scalar_t*)out.data_ptr(), rstd.data_ptr<float>(), (int)rows, H, (float)eps);
     }
@@ -210,8 +260,10 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double 
   return {out, rstd};
 }
 
-std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
-                                           torch::Tensor w, double eps) {
+template <bool GEMMA>
+static std::vector<torch::Tensor> add_rmsnorm_fwd_impl(torch::Tensor x,
+                                                       torch::Tensor resid,
+                                                       torch::Tensor w, double eps) {
   // out_norm = rmsnorm(x + resid); sum_out = x + resid (the new residual).
   // x may also be fp32 split-K partial slabs [nks, rows, H] from
   // skinny_gemm_nc — then x := sum over slabs (launch-boundary reduce).
@@ -225,7 +277,7 @@ std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
   if (x.dim() == 3 && x.scalar_type() == torch::kFloat) {
     TORCH_CHECK(resid.scalar_type() == torch::kBFloat16);
     TORCH_CHECK(x.size(1) * x.size(2) == rows * H);
-    hipLaunchKernelGGL((add_rmsnorm_slab_kernel<bf16, 8>), dim3(grid),
+    hipLaunchKernelGGL((add_rmsnorm_slab_kernel<bf16, 8, GEMMA>), dim3(grid),
       dim3(256), 0, cur_stream(), x.data_ptr<float>(), (int)x.size(0),
       (const bf16*)resid.data_ptr(), (const bf16*)w.data_ptr(),
       (bf16*)out.data_ptr(), (bf16*)sum_out.data_ptr(), (int)rows, H,
@@ -236,7 +288,7 @@ std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
   TORCH_CHECK(x.element_size() == 2);
   DISPATCH_BF16_FP16_FP32(x.scalar_type(), "add_rmsnorm", [&] {
     if constexpr (sizeof(scalar_t) == 2) {
-      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 8, true>), dim3(grid),
+      hipLaunchKernelGGL((rmsnorm_fwd_kernel<scalar_t, 8, true, GEMMA>), dim3(grid),
         dim3(256), 0, cur_stream(), (const scalar_t*)x.data_ptr(),
         (const scalar_t*)w.data_ptr(), (scalar_t*)out.data_ptr(),
         nullptr, (int)rows, H, (float)eps,
@@ -247,8 +299,10 @@ std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
   return {out, sum_out};
 }
 
-std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
-                                       torch::Tensor w, torch::Tensor rstd) {
+template <bool GEMMA>
+static std::vector<torch::Tensor> rmsnorm_bwd_impl(torch::Tensor dy, torch::Tensor x,
+                                                   torch::Tensor w,
+                                                   torch::Tensor rstd) {
   int H = x.size(-1);
   TORCH_CHECK(H <= 256 * RMS_MAX_COLS, "rmsnorm_bwd supports hidden <= 16384");
   long rows = x.numel() / H;
@@ -257,12 +311,12 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto dw32 = torch::zeros({grid, H}, x.options().dtype(torch::kFloat));
   DISPATCH_BF16_FP16_FP32(x.scalar_type(), "rmsnorm_bwd", [&] {
     if (x.element_size() == 2) {
-      hipLaunchKernelGGL((rmsnorm_bwd_kernel<scalar_t, 8>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((rmsnorm_bwd_kernel<scalar_t, 8, GEMMA>), dim3(grid), dim3(RMS_THREADS), 0,
         cur_stream(), (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
         (const scalar_t*)w.data_ptr(), rstd.data_ptr<float>(),
         (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(), (int)rows, H);
     } else {
-      hipLaunchKernelGGL((rmsnorm_bwd_kernel<scalar_t, 4>), dim3(grid), dim3(256), 0,
+      hipLaunchKernelGGL((rmsnorm_bwd_kernel<scalar_t, 4, GEMMA>), dim3(grid), dim3(RMS_THREADS), 0,
         cur_stream(), (const scalar_t*)dy.data_ptr(), (const scalar_t*)x.data_ptr(),
         (const scalar_t*)w.data_ptr(), rstd.data_ptr<float>(),
         (scalar_t*)dx.data_ptr(), dw32.data_ptr<float>(), (int)rows, H);
@@ -270,4 +324,28 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   });
   CHECK_CUDA_OK();
   return {dx, dw32.sum(0).to(x.scalar_type())};
+}
+
+std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps) {
+  return rmsnorm_fwd_impl<false>(x, w, eps);
+}
+std::vector<torch::Tensor> gemma_rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
+                                             double eps) {
+  return rmsnorm_fwd_impl<true>(x, w, eps);
+}
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
+                                           torch::Tensor w, double eps) {
+  return add_rmsnorm_fwd_impl<false>(x, resid, w, eps);
+}
+std::vector<torch::Tensor> gemma_add_rmsnorm_fwd(torch::Tensor x, torch::Tensor resid,
+                                                 torch::Tensor w, double eps) {
+  return add_rmsnorm_fwd_impl<true>(x, resid, w, eps);
+}
+std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                       torch::Tensor w, torch::Tensor rstd) {
+  return rmsnorm_bwd_impl<false>(dy, x, w, rstd);
+}
+std::vector<torch::Tensor> gemma_rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                             torch::Tensor w, torch::Tensor rstd) {
+  return rmsnorm_bwd_impl<true>(dy, x, w, rstd);
 }

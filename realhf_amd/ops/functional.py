@@ -1,9 +1,15 @@
 """Hot ops: HIP kernels with torch reference fallbacks.
 
 HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
-  rms_norm           — fused RMSNorm fwd/bwd (reference used TransformerEngine)
+  rms_norm           — fused RMSNorm fwd/bwd (reference used TransformerEngine);
+                       gemma_style=True is the same kernels in their 1 + w
+                       weight mode
   apply_rotary       — RoPE on packed varlen qk (reference: flash-attn fused rotary)
   swiglu             — silu(gate)*up fused fwd/bwd
+  geglu              — gelu_tanh(gate)*up fused fwd/bwd (gemma), the swiglu
+                       kernels with the activation as a template parameter;
+                       REALHF_AMD_NO_GEMMA_OPS=1 puts gemma's norm and GeGLU
+                       back on torch
   attn_varlen        — flash-attention packed prefill (reference: flash_attn_varlen_func)
   attn_decode        — single-token GQA decode over contiguous KV cache
                        (reference: flash_attn_with_kvcache)
@@ -48,25 +54,38 @@ def gemma_rms_norm_ref(x, weight, eps):
     return (out * (1.0 + weight.float())).to(x.dtype)
 
 
+def gemma_ops_enabled() -> bool:
+    """Gemma's norm and GeGLU run on the HIP kernels unless
+    REALHF_AMD_NO_GEMMA_OPS=1 (read at call time), which restores the torch
+    norm and GeGLU and keeps Gemma out of the decode slab fast paths: the
+    A/B baseline for tests/test_gemma_ops_gpu.py and tools/bench_gemma_ops.py."""
+    return os.environ.get("REALHF_AMD_NO_GEMMA_OPS") != "1"
+
+
 class _RMSNormFn(torch.autograd.Function):
+    """gemma=True scales by 1 + weight (summed in fp32 inside the kernel)."""
+
     @staticmethod
-    def forward(ctx, x, weight, eps):
+    def forward(ctx, x, weight, eps, gemma=False):
         C = _ops.require_hip()
-        out, rstd = C.rmsnorm_fwd(x, weight, eps)
+        fwd = C.gemma_rmsnorm_fwd if gemma else C.rmsnorm_fwd
+        out, rstd = fwd(x, weight, eps)
         ctx.save_for_backward(x, weight, rstd)
+        ctx.gemma = gemma
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         C = _ops.require_hip()
         x, weight, rstd = ctx.saved_tensors
-        dx, dw = C.rmsnorm_bwd(grad_out.contiguous(), x, weight, rstd)
-        return dx, dw, None
+        bwd = C.gemma_rmsnorm_bwd if ctx.gemma else C.rmsnorm_bwd
+        dx, dw = bwd(grad_out.contiguous(), x, weight, rstd)
+        return dx, dw, None, None
 
 
 def rms_norm(x, weight, eps: float = 1e-5, gemma_style: bool = False):
-    if _ops.use_hip(x) and not gemma_style:
-        return _RMSNormFn.apply(x.contiguous(), weight, eps)
+    if _ops.use_hip(x) and (not gemma_style or gemma_ops_enabled()):
+        return _RMSNormFn.apply(x.contiguous(), weight, eps, gemma_style)
     if gemma_style:
         return gemma_rms_norm_ref(x, weight, eps)
     return rms_norm_ref(x, weight, eps)
@@ -206,6 +225,39 @@ def swiglu(gate_up):
     if _ops.use_hip(gate_up):
         return _SwiGLUFn.apply(gate_up.contiguous())
     return swiglu_ref(gate_up)
+
+
+# ---------------------------------------------------------------------------
+# GeGLU epilogue (gemma): gelu_tanh(gate) * up
+# ---------------------------------------------------------------------------
+def geglu_ref(gate_up: torch.Tensor) -> torch.Tensor:
+    """gate_up: [tokens, 2*idim] with gate = [:, :idim], up = [:, idim:]."""
+    gate, up = gate_up.chunk(2, dim=-1)
+    return (
+        torch.nn.functional.gelu(gate.float(), approximate="tanh") * up.float()
+    ).to(gate_up.dtype)
+
+
+class _GeGLUFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gate_up):
+        C = _ops.require_hip()
+        out = C.geglu_fwd(gate_up)
+        ctx.save_for_backward(gate_up)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        C = _ops.require_hip()
+        (gate_up,) = ctx.saved_tensors
+        return C.geglu_bwd(grad.contiguous(), gate_up)
+
+
+def geglu(gate_up):
+    if (_ops.use_hip(gate_up) and gate_up.element_size() == 2
+            and gemma_ops_enabled()):
+        return _GeGLUFn.apply(gate_up.contiguous())
+    return geglu_ref(gate_up)
 
 
 # ---------------------------------------------------------------------------
