@@ -24,6 +24,10 @@ class GenerationHyperparameters:
     temperature: float = 1.0
     use_hip_graph: bool = True  # hipGraph-captured decode step
     force_no_logits_mask: bool = True
+    # FP8 weight-only decode: None | "none" | "fp8_e4m3".  None reads
+    # REALHF_AMD_GEN_WEIGHT_QUANT at generate() time (default "none");
+    # anything else raises there.  See docs/flags.md.
+    weight_quant: Optional[str] = None
 
 
 @dataclasses.dataclass

@@ -15,14 +15,16 @@ Design (MI355X-first):
 - termination: all sequences hit EOS or max_new_tokens; min_new_tokens
   masks EOS early.
 """
+import contextlib
 import dataclasses
 import os
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
 from realhf_amd.api.model import GenerationHyperparameters
 from realhf_amd.base import logging
+from realhf_amd.models.layers import ReaLModelBlock
 from realhf_amd.models.real_model import ReaLModel
 from realhf_amd.ops import functional as ops
 from realhf_amd.utils.functional import top_k_top_p_logits  # noqa: F401 — re-exported for interface use
@@ -146,22 +148,133 @@ class DecodeGraph:
         self.graph = None
 
 
+WEIGHT_QUANT_MODES = ("none", "fp8_e4m3")
+
+
+def resolve_weight_quant(gconfig: GenerationHyperparameters) -> str:
+    """The requested decode weight format: the gconfig field when set, else
+    REALHF_AMD_GEN_WEIGHT_QUANT read now (default "none")."""
+    mode = gconfig.weight_quant
+    if mode is None:
+        mode = os.environ.get("REALHF_AMD_GEN_WEIGHT_QUANT") or "none"
+    if mode not in WEIGHT_QUANT_MODES:
+        raise ValueError(
+            f"weight_quant must be one of {WEIGHT_QUANT_MODES} or None, "
+            f"got {mode!r}")
+    return mode
+
+
+def weight_quant_blocker(model: ReaLModel) -> Optional[str]:
+    """Why FP8 weight-only decode cannot be used with this model (None if it
+    can): every case in which the fused decode block, the only reader of
+    the quantized weights on the GPU, is not what runs."""
+    cfg = model.config
+    if getattr(model, "lora_flat", None) is not None:
+        return "LoRA adapters are attached"
+    if cfg.qk_layernorm:
+        return "qk_layernorm"
+    if cfg.head_dim not in ops.HIP_ATTN_HEAD_DIMS:
+        return f"head_dim {cfg.head_dim} not in {ops.HIP_ATTN_HEAD_DIMS}"
+    if model.dtype != torch.bfloat16:
+        return f"model dtype {model.dtype} is not bfloat16"
+    if os.environ.get("REALHF_AMD_NO_FUSED_DECODE") == "1":
+        return "REALHF_AMD_NO_FUSED_DECODE=1"
+    if model.pp_size > 1:
+        return "pp > 1 generation"
+    return None
+
+
+def effective_weight_quant(model: ReaLModel,
+                           gconfig: GenerationHyperparameters) -> str:
+    """resolve_weight_quant, downgraded to "none" (one logged warning per
+    model) where weight_quant_blocker names a reason."""
+    mode = resolve_weight_quant(gconfig)
+    if mode == "none":
+        return mode
+    why = weight_quant_blocker(model)
+    if why is None:
+        return mode
+    if not getattr(model, "_weight_quant_warned", False):
+        logger.warning("weight_quant=%s ignored for this model: %s; "
+                       "decoding with bf16 weights", mode, why)
+        model._weight_quant_warned = True
+    return "none"
+
+
+class Fp8DecodeWeights:
+    """One persistent (q, scale) pair per decode projection (merged QKV, wo,
+    merged gate/up, down) of every local block.  A projection whose shape
+    the fp8 kernel does not take (N or K not a multiple of 64) has no pair
+    and keeps its bf16 weight.  refresh() re-quantizes in place from the
+    current flat_param views, so a captured graph keeps reading the same
+    addresses; installed() hands the pairs to the blocks for one generate()."""
+
+    def __init__(self, model: ReaLModel):
+        self.blocks = [b for b in model.layers if isinstance(b, ReaLModelBlock)]
+        self.pairs = []  # per block: key -> (q, scale)
+        for blk in self.blocks:
+            d: Dict[str, tuple] = {}
+            for key, w in blk.decode_weights().items():
+                n, k = w.shape
+                if n % 64 or k % 64:
+                    continue
+                d[key] = (
+                    torch.empty(n, k, dtype=torch.float8_e4m3fn, device=w.device),
+                    torch.empty(n, dtype=torch.float32, device=w.device),
+                )
+            self.pairs.append(d)
+
+    def nbytes(self) -> int:
+        return sum(q.numel() + 4 * s.numel()
+                   for d in self.pairs for q, s in d.values())
+
+    def refresh(self):
+        for blk, d in zip(self.blocks, self.pairs):
+            ws = blk.decode_weights()
+            for key, pair in d.items():
+                ops.quantize_rows_e4m3(ws[key], out=pair)
+
+    @contextlib.contextmanager
+    def installed(self):
+        for blk, d in zip(self.blocks, self.pairs):
+            blk.fp8 = d
+        try:
+            yield self
+        finally:
+            for blk in self.blocks:
+                blk.fp8 = {}
+
+
 class GenerationSession:
     """Persistent KV caches + captured decode graph, reused across generate
     calls of the same shape (the capture costs ~100 eager layer launches;
-    re-capturing per call was ~2 s/step at the 7B bench shape)."""
+    re-capturing per call was ~2 s/step at the 7B bench shape).  With
+    weight_quant="fp8_e4m3" it also owns the quantized decode weights."""
 
-    def __init__(self, kv_caches, decoder):
+    def __init__(self, kv_caches, decoder, fp8: Optional[Fp8DecodeWeights] = None):
         self.kv_caches = kv_caches
         self.decoder = decoder
+        self.fp8 = fp8
 
 
-def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device):
+def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str):
+    """The quant mode is part of the key: the captured graph has the weight
+    format baked in (and, for fp8, whether the kernel or the
+    REALHF_AMD_NO_FP8_SKINNY reference reads it)."""
+    key = (bs, cache_len, id(model.flat_param), weight_quant)
+    if weight_quant != "none":
+        key += (ops.fp8_skinny_enabled(),)
+    return key
+
+
+def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device,
+                 weight_quant: str = "none"):
     cfg = model.config
-    key = (bs, cache_len, id(model.flat_param))
+    key = _session_key(model, bs, cache_len, weight_quant)
     sess = getattr(model, "_gen_session", None)
     if sess is not None and sess[0] == key:
         return sess[1]
+    model._gen_session = None  # drop the old caches before allocating
     n_blocks = sum(1 for i in model.layer_indices if 1 <= i <= cfg.n_layers)
     kv_caches = [
         (
@@ -172,7 +285,8 @@ def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device):
         )
         for _ in range(n_blocks)
     ]
-    s = GenerationSession(kv_caches, DecodeGraph(model, kv_caches, bs))
+    fp8 = Fp8DecodeWeights(model) if weight_quant == "fp8_e4m3" else None
+    s = GenerationSession(kv_caches, DecodeGraph(model, kv_caches, bs), fp8)
     model._gen_session = (key, s)
     return s
 
@@ -216,8 +330,33 @@ def generate(
     # same session/graph
     cache_len = ((max_prompt + max_new + 127) // 128) * 128
 
+    weight_quant = effective_weight_quant(model, gconfig)
     nkv_local = max(cfg.n_kv_heads // model.tp_size, 1)
-    sess = _get_session(model, bs, cache_len, nkv_local, device)
+    sess = _get_session(model, bs, cache_len, nkv_local, device, weight_quant)
+    if sess.fp8 is None:
+        return _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens,
+                         max_prompt, gconfig, eos_token_id, pad_token_id,
+                         generator, return_prompt_logprobs)
+    # FP8 weight-only decode: re-quantize from the current flat_param on
+    # EVERY call (the optimizer writes it through a kernel no version
+    # counter sees; the caller has already waited any deferred parameter
+    # all-gather), in place, so a captured graph keeps its addresses.  The
+    # pairs are visible to the blocks for this call only, and only decode
+    # steps read them: prefill stays bf16.
+    sess.fp8.refresh()
+    with sess.fp8.installed():
+        return _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens,
+                         max_prompt, gconfig, eos_token_id, pad_token_id,
+                         generator, return_prompt_logprobs)
+
+
+def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
+              gconfig, eos_token_id, pad_token_id, generator,
+              return_prompt_logprobs):
+    cfg = model.config
+    device = packed_prompts.device
+    bs = cu_seqlens.shape[0] - 1
+    max_new = gconfig.max_new_tokens
     kv_caches = sess.kv_caches
 
     # ---- prefill --------------------------------------------------------

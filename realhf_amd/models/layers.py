@@ -132,16 +132,42 @@ class ReaLModelBlock(nn.Module):
         # ("wq"/"wk"/"wv"/"wo") -> (A [r, in], B [out, r]) views
         self.lora: Dict[str, tuple] = {}
         self.lora_scale = 0.0
+        # FP8 weight-only decode: "qkv" / "wo" / "gu" / "down" -> (q, scale)
+        # of that projection, installed by the generation session for the
+        # span of one generate() call and read by decode steps only
+        self.fp8: Dict[str, tuple] = {}
+
+    def decode_weights(self) -> Dict[str, torch.Tensor]:
+        """The decode step's projection weights as the fused decode block
+        reads them (merged QKV and gate/up views where the flat layout
+        gives them); MoE expert weights are not among them."""
+        i = self.i
+        out = {}
+        qkv = _maybe_merged(self.p, self._qkv_names,
+                            (self.nq + 2 * self.nkv) * self.hd)
+        if qkv is not None:
+            out["qkv"] = qkv
+        out["wo"] = self.p[f"{i}.attn.wo.weight"]
+        if self.moe is None:
+            if self._gu_names is not None:
+                idim_local = self.p[f"{i}.mlp.gate.weight"].shape[0]
+                gu = _maybe_merged(self.p, self._gu_names, 2 * idim_local)
+                if gu is not None:
+                    out["gu"] = gu
+            out["down"] = self.p[f"{i}.mlp.down.weight"]
+        return out
 
     def _lora_delta(self, x, short: str):
         a, b = self.lora[short]
         return ((x @ a.t()) @ b.t()) * self.lora_scale
 
     # -- attention --------------------------------------------------------
-    def _qkv(self, x, fused_sp=None):
+    def _qkv(self, x, fused_sp=None, fp8=None):
         qkv_dim = (self.nq + 2 * self.nkv) * self.hd
         merged = _maybe_merged(self.p, self._qkv_names, qkv_dim)
-        if fused_sp is not None and merged is not None:
+        if fp8 is not None and merged is not None:
+            qkv = ops.maybe_skinny_linear(x, merged, fp8=fp8)
+        elif fused_sp is not None and merged is not None:
             # x is PRE-mapping: the fused fn applies (copy|SP-gather) in
             # forward and overlaps the bwd grad collective with the
             # weight-grad GEMM (mappings._ColumnParallelLinear)
@@ -190,6 +216,8 @@ class ReaLModelBlock(nn.Module):
     ):
         i = self.i
         cfg = self.cfg
+        # prefill and training never read the quantized weights
+        fp8 = self.fp8 if decode else {}
         h = _norm(cfg, x, self.p[f"{i}.attn.ln.weight"], self.p.get(f"{i}.attn.ln.bias"))
         sp = constants.has_current() and constants.sequence_parallel()
         # fused column linear (async bwd comm) takes the PRE-mapping h;
@@ -227,9 +255,10 @@ class ReaLModelBlock(nn.Module):
             if merged is not None:
                 # launch-boundary reduce: hand the split-K fp32 slabs
                 # straight to rope_qkv_decode's prologue (no combine pass)
-                qkv_raw = ops.skinny_linear_nc(h, merged)
+                qkv_raw = ops.skinny_linear_nc(h, merged, fp8=fp8.get("qkv"))
                 if qkv_raw is None:
-                    qkv_raw = ops.maybe_skinny_linear(h, merged)
+                    qkv_raw = ops.maybe_skinny_linear(h, merged,
+                                                      fp8=fp8.get("qkv"))
                 if qkv_raw is None:
                     qkv_raw = _linear(h, merged)
             else:
@@ -270,14 +299,14 @@ class ReaLModelBlock(nn.Module):
             ):
                 # launch-boundary reduce: o's split-K slabs are summed in
                 # the fused add+rmsnorm prologue (no combine, no bf16 o)
-                o_parts = ops.skinny_linear_nc(attn_out, wo)
+                o_parts = ops.skinny_linear_nc(attn_out, wo, fp8=fp8.get("wo"))
                 if o_parts is not None:
                     h2, x2 = add_norm(
                         o_parts, x, self.p[f"{i}.mlp.ln.weight"],
                         cfg.layer_norm_epsilon,
                     )
-                    return self._mlp_body(h2, sp, residual=x2)
-            o = ops.maybe_skinny_linear(attn_out, wo)
+                    return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
+            o = ops.maybe_skinny_linear(attn_out, wo, fp8=fp8.get("wo"))
             if o is None:
                 o = _linear(attn_out, wo)
             o = mappings.reduce_from_tp_region(o)
@@ -289,11 +318,12 @@ class ReaLModelBlock(nn.Module):
                 h2, x2 = add_norm(
                     o, x, self.p[f"{i}.mlp.ln.weight"], cfg.layer_norm_epsilon
                 )
-                return self._mlp_body(h2, sp, residual=x2)
+                return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
             x = x + o
-            return self._mlp(x, sp)
+            return self._mlp(x, sp, fp8=fp8)
 
-        q, k, v = self._qkv(h, fused_sp=(sp if fused_col else None))
+        q, k, v = self._qkv(h, fused_sp=(sp if fused_col else None),
+                            fp8=fp8.get("qkv"))
         if cfg.apply_rotary:
             # graph-capture-safe length bound: never read positions back
             if decode:
@@ -378,7 +408,11 @@ class ReaLModelBlock(nn.Module):
                     softmax_scale=scale, window=cfg.sliding_window,
                 )
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
-        o = _linear(attn_out, self.p[f"{i}.attn.wo.weight"])
+        if "wo" in fp8:
+            o = ops.maybe_skinny_linear(attn_out, self.p[f"{i}.attn.wo.weight"],
+                                        fp8=fp8["wo"])
+        else:
+            o = _linear(attn_out, self.p[f"{i}.attn.wo.weight"])
         if "wo" in self.lora:
             o = o + self._lora_delta(attn_out, "wo")
         if sp:
@@ -388,22 +422,24 @@ class ReaLModelBlock(nn.Module):
         if f"{i}.attn.wo.bias" in self.p:
             o = o + self.p[f"{i}.attn.wo.bias"]
         x = x + o
-        return self._mlp(x, sp)
+        return self._mlp(x, sp, fp8=fp8)
 
-    def _mlp(self, x, sp):
+    def _mlp(self, x, sp, fp8=None):
         cfg = self.cfg
         i = self.i
         h = _norm(cfg, x, self.p[f"{i}.mlp.ln.weight"], self.p.get(f"{i}.mlp.ln.bias"))
         if self.moe is not None:
             return x + self.moe(h)
-        return x + self._mlp_body(h, sp)  # residual not folded here
+        return x + self._mlp_body(h, sp, fp8=fp8)  # residual not folded here
 
-    def _mlp_body(self, h, sp, residual=None):
+    def _mlp_body(self, h, sp, residual=None, fp8=None):
         """norm-output -> MLP delta; with `residual` (tp==1 decode path)
         the down-projection's combine kernel adds it in and the return
-        value is the full residual-stream output."""
+        value is the full residual-stream output.  fp8: the decode step's
+        (q, scale) pairs for "gu" and "down" (FP8 weight-only decode)."""
         cfg = self.cfg
         i = self.i
+        fp8 = fp8 or {}
         fused_col = self.tp_size > 1 and torch.is_grad_enabled()
         if fused_col and cfg.activation in ("silu", "geglu"):
             idim_local = self.p[f"{i}.mlp.gate.weight"].shape[0]
@@ -428,7 +464,8 @@ class ReaLModelBlock(nn.Module):
                     cfg.activation == "silu" or ops.gemma_ops_enabled()
                 ):
                     # launch-boundary reduce: slabs summed in swiglu/geglu
-                    gu_parts = ops.skinny_linear_nc(h, merged)
+                    gu_parts = ops.skinny_linear_nc(h, merged,
+                                                    fp8=fp8.get("gu"))
                     if gu_parts is not None:
                         from realhf_amd import ops as _ops_pkg
 
@@ -436,7 +473,7 @@ class ReaLModelBlock(nn.Module):
                         act = (C.swiglu_fwd if cfg.activation == "silu"
                                else C.geglu_fwd)(gu_parts)
                 if act is None:
-                    gu = ops.maybe_skinny_linear(h, merged)
+                    gu = ops.maybe_skinny_linear(h, merged, fp8=fp8.get("gu"))
                     if gu is None:
                         gu = _linear(h, merged)
             elif not fused_col:
@@ -455,7 +492,8 @@ class ReaLModelBlock(nn.Module):
         wd = self.p[f"{i}.mlp.down.weight"]
         use_resid_fold = residual is not None and self.tp_size == 1
         down = ops.maybe_skinny_linear(
-            act, wd, residual=residual if use_resid_fold else None
+            act, wd, residual=residual if use_resid_fold else None,
+            fp8=fp8.get("down"),
         )
         folded = down is not None and use_resid_fold
         if down is None:

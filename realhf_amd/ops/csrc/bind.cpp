@@ -81,6 +81,17 @@ std::vector<torch::Tensor> vocab_logprob_fwd(torch::Tensor logits,
 torch::Tensor vocab_logprob_bwd(torch::Tensor logits, torch::Tensor labels,
                                 torch::Tensor lse, torch::Tensor grad_out,
                                 long vocab_start, long ignore_index);
+// FP8 weight-only decode: per-row e4m3 quantizer (q one byte per element,
+// scale fp32 [N]) and the skinny GEMM that streams q instead of bf16 W
+std::vector<torch::Tensor> quantize_rows_e4m3(torch::Tensor w);
+void quantize_rows_e4m3_(torch::Tensor w, torch::Tensor q, torch::Tensor scale);
+torch::Tensor skinny_gemm_fp8(torch::Tensor x, torch::Tensor q,
+                              torch::Tensor scale, torch::Tensor out32_ws,
+                              long splitk,
+                              c10::optional<torch::Tensor> residual);
+torch::Tensor skinny_gemm_fp8_nc(torch::Tensor x, torch::Tensor q,
+                                 torch::Tensor scale, torch::Tensor out32_ws,
+                                 long splitk);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -122,4 +133,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mcmc_search", &mcmc_search);
   m.def("vocab_logprob_fwd", &vocab_logprob_fwd);
   m.def("vocab_logprob_bwd", &vocab_logprob_bwd);
+  m.def("quantize_rows_e4m3", &quantize_rows_e4m3);
+  m.def("quantize_rows_e4m3_", &quantize_rows_e4m3_);
+  m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
+  m.def("skinny_gemm_fp8_nc", &skinny_gemm_fp8_nc);
 }

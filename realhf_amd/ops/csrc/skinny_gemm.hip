@@ -358,3 +358,164 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
   CHECK_CUDA_OK();
   return out;
 }
+
+// ---------------------------------------------------------------------------
+// FP8 weight-only variant: W is stored as OCP e4m3fn codes q[N, K] (one
+// byte per element) with one fp32 scale per row, W[n, k] = q[n, k] *
+// scale[n] (quantize_fp8.hip).  x stays bf16; half the weight bytes are
+// streamed.
+//
+// Fragment mapping.  The W stream keeps its 16 bytes per lane, which is now
+// 16 k-elements, so one load feeds TWO mfma16 steps and the k body is 64
+// deep per load.  Lane (i16, g) owns k in [g*16, g*16 + 16) of each
+// 64-block: its low 8 bytes are the B fragment of the first MFMA, its high
+// 8 bytes of the second.  An MFMA sums over k in whatever order the lanes
+// present it, provided A and B agree: mfma.h puts logical k = g*8 + j in
+// lane (i16, g) slot j of both operands, so the A fragments are read from
+// x_s at the SAME physical offsets, x_s[i16][g*16 + 0..7] and
+// x_s[i16][g*16 + 8..15].
+//
+// Conversion.  e4m3 -> f32 by v_cvt_pk_f32_fp8 (subnormals included), then
+// the upper 16 bits are the bf16: exact, an e4m3 value has 3 mantissa bits
+// and bf16 keeps 7.  The MFMA therefore sees q exactly, and the row scale is
+// applied once per output in the epilogue, before the fp32 partial is
+// stored: the slabs mean what the bf16 kernel's slabs mean and every slab
+// consumer (sg_combine_kernel, rope_qkv_decode, add_rmsnorm, swiglu/geglu)
+// is unchanged.
+typedef __attribute__((ext_vector_type(4))) int int4v;
+typedef __attribute__((ext_vector_type(2))) float float2v;
+
+DEVINL unsigned sg_bf16_pair(float lo, float hi) {
+  return (__builtin_bit_cast(unsigned, lo) >> 16) |
+         (__builtin_bit_cast(unsigned, hi) & 0xffff0000u);
+}
+
+// 8 consecutive e4m3 bytes (lo = bytes 0..3, hi = 4..7) -> bf16x8, in order
+DEVINL bf16x8 sg_e4m3x8_to_bf16(int lo, int hi) {
+  const float2v p0 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false);
+  const float2v p1 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+  const float2v p2 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false);
+  const float2v p3 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+  int4v u;
+  u[0] = (int)sg_bf16_pair(p0[0], p0[1]);
+  u[1] = (int)sg_bf16_pair(p1[0], p1[1]);
+  u[2] = (int)sg_bf16_pair(p2[0], p2[1]);
+  u[3] = (int)sg_bf16_pair(p3[0], p3[1]);
+  return __builtin_bit_cast(bf16x8, u);
+}
+
+// NB x 64-deep k body: NB 16-byte q loads in flight per lane, 2*NB MFMAs
+template <int NB>
+__global__ __launch_bounds__(256, 4) void skinny_gemm_fp8_kernel(
+    const bf16* __restrict__ x, const unsigned char* __restrict__ q,
+    const float* __restrict__ scale, float* __restrict__ out32, int M, int N,
+    int K, int kslice) {
+  const int ntile = blockIdx.x;
+  const int ks = blockIdx.y;
+  const int k_lo = ks * kslice;
+  const int k_hi = min(K, k_lo + kslice);  // K, kslice % 64 == 0
+  const auto [lane, wv, i16, g] = mfma_lane();
+  const int n0 = ntile * SG_TN + wv * 16;
+
+  extern __shared__ __bf16 x_s[];  // [16][kslice] rows (zero-padded m >= M)
+  sg_stage_x<256>(x_s, x, M, K, k_lo, k_hi, kslice);
+  __syncthreads();
+
+  f32x4 acc[4] = {};
+  const unsigned char* qrow = q + (long)(n0 + i16) * K + g * 16;
+  // x_s index of this lane's k = kk is xo + kk (kk >= k_lo)
+  const int xo = i16 * kslice + g * 16 - k_lo;
+  int kk = k_lo;
+  for (; kk + NB * 64 <= k_hi; kk += NB * 64) {
+    int4v b[NB];
+    #pragma unroll
+    for (int t = 0; t < NB; t++)
+      b[t] = *(const int4v*)(qrow + kk + t * 64);
+    bf16x8 a[2 * NB];
+    #pragma unroll
+    for (int t = 0; t < NB; t++) {
+      a[2 * t] = *(const bf16x8*)(&x_s[xo + kk + t * 64]);
+      a[2 * t + 1] = *(const bf16x8*)(&x_s[xo + kk + t * 64 + 8]);
+    }
+    #pragma unroll
+    for (int t = 0; t < NB; t++) {
+      acc[(2 * t) & 3] = mfma16(a[2 * t], sg_e4m3x8_to_bf16(b[t][0], b[t][1]),
+                                acc[(2 * t) & 3]);
+      acc[(2 * t + 1) & 3] = mfma16(a[2 * t + 1],
+                                    sg_e4m3x8_to_bf16(b[t][2], b[t][3]),
+                                    acc[(2 * t + 1) & 3]);
+    }
+  }
+  for (; kk + 64 <= k_hi; kk += 64) {
+    const int4v b0 = *(const int4v*)(qrow + kk);
+    const bf16x8 a0 = *(const bf16x8*)(&x_s[xo + kk]);
+    const bf16x8 a1 = *(const bf16x8*)(&x_s[xo + kk + 8]);
+    acc[0] = mfma16(a0, sg_e4m3x8_to_bf16(b0[0], b0[1]), acc[0]);
+    acc[1] = mfma16(a1, sg_e4m3x8_to_bf16(b0[2], b0[3]), acc[1]);
+  }
+  // row scale once per output, then the per-K-slice partial out32[ks][m][n]
+  const float sc = scale[n0 + i16];
+  #pragma unroll
+  for (int r = 0; r < 4; r++) {
+    int m = g * 4 + r;
+    float vsum = acc[0][r] + acc[1][r] + acc[2][r] + acc[3][r];
+    if (m < M)
+      out32[((long)ks * M + m) * N + n0 + i16] = vsum * sc;
+  }
+}
+
+// q [N, K] one byte per element (e4m3 codes), rows contiguous; scale fp32 [N]
+static SgShape sg_shape_fp8(const torch::Tensor& x, const torch::Tensor& q,
+                            const torch::Tensor& scale,
+                            const torch::Tensor& out32_ws, long splitk) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 2 && q.element_size() == 1 &&
+              q.is_contiguous() && (uintptr_t)q.data_ptr() % 16 == 0,
+              "q must be contiguous, 16-byte aligned [N, K] e4m3 bytes");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == q.size(1), "x / q K mismatch");
+  TORCH_CHECK(q.size(1) % 64 == 0, "fp8 skinny GEMM needs K % 64 == 0");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat32 &&
+              scale.is_contiguous() && scale.numel() == q.size(0),
+              "scale must be contiguous fp32 [N]");
+  TORCH_CHECK(out32_ws.is_cuda() && out32_ws.scalar_type() == torch::kFloat32);
+  return sg_shape(x, q, out32_ws, splitk);
+}
+
+static torch::Tensor sg_partials_fp8(const torch::Tensor& x,
+                                     const torch::Tensor& q,
+                                     const torch::Tensor& scale,
+                                     const torch::Tensor& out32_ws,
+                                     const SgShape& s) {
+  auto out32 = out32_ws.narrow(0, 0, (long)s.nks * s.M * s.N)
+                   .view({(long)s.nks, (long)s.M, (long)s.N});
+  hipLaunchKernelGGL((skinny_gemm_fp8_kernel<4>), dim3(s.N / SG_TN, s.nks),
+    dim3(256), s.lds, cur_stream(), (const bf16*)x.data_ptr(),
+    (const unsigned char*)q.data_ptr(), scale.data_ptr<float>(),
+    out32.data_ptr<float>(), s.M, s.N, s.K, s.kslice);
+  return out32;
+}
+
+torch::Tensor skinny_gemm_fp8_nc(torch::Tensor x, torch::Tensor q,
+                                 torch::Tensor scale, torch::Tensor out32_ws,
+                                 long splitk) {
+  auto out32 = sg_partials_fp8(x, q, scale, out32_ws,
+                               sg_shape_fp8(x, q, scale, out32_ws, splitk));
+  CHECK_CUDA_OK();
+  return out32;
+}
+
+torch::Tensor skinny_gemm_fp8(torch::Tensor x, torch::Tensor q,
+                              torch::Tensor scale, torch::Tensor out32_ws,
+                              long splitk,
+                              c10::optional<torch::Tensor> residual) {
+  const SgShape s = sg_shape_fp8(x, q, scale, out32_ws, splitk);
+  auto out32 = sg_partials_fp8(x, q, scale, out32_ws, s);
+  auto out = torch::empty({s.M, (long)s.N}, x.options());
+  long n = (long)s.M * s.N;
+  int cgrid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
+  const bf16* rptr = sg_resid_ptr(residual, n);
+  hipLaunchKernelGGL(sg_combine_kernel, dim3(cgrid), dim3(256), 0,
+    cur_stream(), out32.data_ptr<float>(), rptr, (bf16*)out.data_ptr(), n,
+    s.nks);
+  CHECK_CUDA_OK();
+  return out;
+}

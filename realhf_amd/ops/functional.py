@@ -19,6 +19,11 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
   fused_adamw        — flat-buffer AdamW (reference: apex fused adam via Megatron)
   vocab_logprobs     — per-token log-prob over a vocab slice, fwd/bwd without
                        fp32 [tokens, vocab] temporaries (opt-in, see parallel/tp.py)
+  quantize_rows_e4m3 — per-row OCP e4m3 weight quantizer (q, scale) for FP8
+                       weight-only decode; maybe_skinny_linear /
+                       skinny_linear_nc take the pair as fp8=(q, scale) and
+                       stream q instead of the bf16 weight
+                       (REALHF_AMD_NO_FP8_SKINNY=1: fp8_linear_ref instead)
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -692,7 +697,16 @@ def merge_intervals(intervals: List[Tuple[int, int]]) -> List[Tuple[int, int]]:
 # callers pick per shape (tools/bench_skinny.py is the A/B harness).
 # ---------------------------------------------------------------------------
 def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
-                        residual: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+                        residual: Optional[torch.Tensor] = None,
+                        fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                        ) -> Optional[torch.Tensor]:
+    """fp8 = (q, scale) from quantize_rows_e4m3(w): stream the e4m3 codes
+    instead of w (skinny_gemm_fp8) under the same eligibility rules plus
+    K % 64 == 0.  With a pair the result is never None: whatever the kernel
+    does not take (CPU, M > 16, REALHF_AMD_NO_FP8_SKINNY=1) goes through
+    fp8_linear_ref, so the weights in use are the quantized ones either way."""
+    if fp8 is not None:
+        w = fp8[0]
     if not (
         x.is_cuda
         and x.dtype == torch.bfloat16
@@ -703,7 +717,8 @@ def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
         and x.stride(0) == x.shape[1]
         and w.stride(1) == 1
         and w.shape[0] % 64 == 0
-        and w.shape[1] % 32 == 0
+        and w.shape[1] % (32 if fp8 is None else 64) == 0
+        and (fp8 is None or fp8_skinny_enabled())
         # in-context the weight-streaming kernel also edges out hipBLASLt
         # on the wide-N shapes (A/B: 3.09 vs 3.05 samples/s); opt out with
         # REALHF_AMD_NO_SKINNY_WIDE=1
@@ -713,6 +728,8 @@ def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
         )
         and _ops.hip_available()
     ):
+        if fp8 is not None:
+            return fp8_linear_ref(x, fp8[0], fp8[1], residual)
         return None
     from realhf_amd.base.constants import get_global_memory_buffer
 
@@ -727,6 +744,8 @@ def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
     )
     if residual is not None:
         residual = residual.contiguous()
+    if fp8 is not None:
+        return C.skinny_gemm_fp8(x, fp8[0], fp8[1], ws, splitk, residual)
     if os.environ.get("REALHF_AMD_SKINNY_V2") == "1":
         # v2 (in-launch semaphore combine) measured SLOWER at every decode
         # shape: the per-block agent-scope release (buffer_wbl2) does not
@@ -748,12 +767,19 @@ def _sg_kslice_max() -> int:
 _SG_KSLICE = None
 
 
-def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]:
+def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor,
+                     fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                     ) -> Optional[torch.Tensor]:
     """Like maybe_skinny_linear but WITHOUT the split-K combine: returns
     the fp32 partial slabs [nks, M, N], to be summed in the CONSUMING
     kernel's prologue (launch-boundary reduce: rope_qkv_decode /
     add_rmsnorm_fwd / swiglu_fwd all accept slabs).  The slabs live in the
-    shared skinny workspace — consume them before the next skinny call."""
+    shared skinny workspace — consume them before the next skinny call.
+    fp8 = (q, scale): the slabs come from skinny_gemm_fp8_nc, row scale
+    already applied; None where that kernel does not apply (the caller then
+    goes on to maybe_skinny_linear with the same pair)."""
+    if fp8 is not None:
+        w = fp8[0]
     if not (
         x.is_cuda
         and x.dtype == torch.bfloat16
@@ -764,7 +790,8 @@ def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]
         and x.stride(0) == x.shape[1]
         and w.stride(1) == 1
         and w.shape[0] % 64 == 0
-        and w.shape[1] % 32 == 0
+        and w.shape[1] % (32 if fp8 is None else 64) == 0
+        and (fp8 is None or fp8_skinny_enabled())
         and _ops.hip_available()
     ):
         return None
@@ -779,6 +806,8 @@ def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor) -> Optional[torch.Tensor]
     ws = get_global_memory_buffer().get_tensor(
         (2 * splitk * 16 * N,), torch.float32, "skinny_gemm_ws"
     )
+    if fp8 is not None:
+        return C.skinny_gemm_fp8_nc(x, fp8[0], fp8[1], ws, splitk)
     return C.skinny_gemm_nc(x, w, ws, splitk)
 
 
@@ -794,6 +823,59 @@ def _skinny_sem(device) -> torch.Tensor:
         t = torch.zeros(1024, dtype=torch.int32, device=device)
         _SKINNY_SEM[device] = t
     return t
+
+
+# ---------------------------------------------------------------------------
+# FP8 weight-only decode: per-row e4m3 quantizer and its linear reference
+# ---------------------------------------------------------------------------
+E4M3_MAX = 448.0
+
+
+def quantize_rows_e4m3_ref(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(q [N, K] float8_e4m3fn, scale [N] fp32) with scale = amax / 448 per
+    row (1 for an all-zero row) and q = rne_e4m3(float(w) / scale).  The
+    fixed definition the HIP quantizer matches bit for bit.  Rows with
+    non-finite weights get no special handling."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / E4M3_MAX)
+    return (wf / scale[:, None]).to(torch.float8_e4m3fn), scale
+
+
+def quantize_rows_e4m3(w: torch.Tensor, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Quantize bf16 w [N, K] (stride(1) == 1, any row stride) per row.
+    out = (q, scale) writes into caller-owned buffers (stable addresses for
+    a captured graph) and returns them."""
+    if _ops.use_hip(w):
+        C = _ops.require_hip()
+        if out is None:
+            q, scale = C.quantize_rows_e4m3(w)
+            return q, scale
+        C.quantize_rows_e4m3_(w, out[0], out[1])
+        return out
+    q, scale = quantize_rows_e4m3_ref(w)
+    if out is None:
+        return q, scale
+    out[0].copy_(q)
+    out[1].copy_(scale)
+    return out
+
+
+def fp8_skinny_enabled() -> bool:
+    """(q, scale) weights run on skinny_gemm_fp8 unless
+    REALHF_AMD_NO_FP8_SKINNY=1 (read at call time), which sends the same
+    pair through fp8_linear_ref: the A/B baseline and the oracle of
+    tests/test_fp8_decode_gpu.py."""
+    return os.environ.get("REALHF_AMD_NO_FP8_SKINNY") != "1"
+
+
+def fp8_linear_ref(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor,
+                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x @ (q * scale[:, None])^T (+ residual) in fp32, returned in x.dtype."""
+    out = x.float() @ (q.float() * scale[:, None]).t()
+    if residual is not None:
+        out = out + residual.float()
+    return out.to(x.dtype)
 
 
 # ---------------------------------------------------------------------------

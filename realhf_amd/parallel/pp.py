@@ -299,6 +299,9 @@ class PipelinedEngine(PipelinableEngine):
         self.model.eval()
         g = self._grid()
         gconfig = gconfig or GenerationHyperparameters()
+        # FP8 weight-only decode belongs to the pp == 1 session: validated
+        # here, then ignored with one warning (bf16 weights)
+        genmod.effective_weight_quant(self.model, gconfig)
         cfg = self.model.config
         dev = self.model.flat_param.device
         dtype = self.model.dtype

@@ -27,6 +27,7 @@ SRC = [
     "realhf_amd/ops/csrc/all_reduce.hip",
     "realhf_amd/ops/csrc/attn_bwd.hip",
     "realhf_amd/ops/csrc/logprob.hip",
+    "realhf_amd/ops/csrc/quantize_fp8.hip",
 ]
 
 setup(
