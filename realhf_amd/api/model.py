@@ -28,6 +28,10 @@ class GenerationHyperparameters:
     # REALHF_AMD_GEN_WEIGHT_QUANT at generate() time (default "none");
     # anything else raises there.  See docs/flags.md.
     weight_quant: Optional[str] = None
+    # FP8 (e4m3) KV cache for generation: None | "none" | "fp8_e4m3".  None
+    # reads REALHF_AMD_GEN_KV_QUANT at generate() time (default "none");
+    # anything else raises there.  Composes with weight_quant.
+    kv_quant: Optional[str] = None
 
 
 @dataclasses.dataclass

@@ -201,6 +201,59 @@ def effective_weight_quant(model: ReaLModel,
     return "none"
 
 
+KV_QUANT_MODES = ("none", "fp8_e4m3")
+
+
+def resolve_kv_quant(gconfig: GenerationHyperparameters) -> str:
+    """The requested KV cache format: the gconfig field when set, else
+    REALHF_AMD_GEN_KV_QUANT read now (default "none")."""
+    mode = gconfig.kv_quant
+    if mode is None:
+        mode = os.environ.get("REALHF_AMD_GEN_KV_QUANT") or "none"
+    if mode not in KV_QUANT_MODES:
+        raise ValueError(
+            f"kv_quant must be one of {KV_QUANT_MODES} or None, got {mode!r}")
+    return mode
+
+
+def kv_quant_blocker(model: ReaLModel) -> Optional[str]:
+    """Why the FP8 KV cache cannot be used with this model (None if it can).
+    On the GPU the fused decode block is the only writer of the quantized
+    cache, so weight_quant_blocker's cases apply; on the CPU the torch
+    references write and read it and any model dtype is fine."""
+    cfg = model.config
+    if getattr(model, "lora_flat", None) is not None:
+        return "LoRA adapters are attached"
+    if cfg.qk_layernorm:
+        return "qk_layernorm"
+    if cfg.head_dim not in ops.HIP_ATTN_HEAD_DIMS:
+        return f"head_dim {cfg.head_dim} not in {ops.HIP_ATTN_HEAD_DIMS}"
+    if model.flat_param.is_cuda and model.dtype != torch.bfloat16:
+        return f"model dtype {model.dtype} on the GPU is not bfloat16"
+    if os.environ.get("REALHF_AMD_NO_FUSED_DECODE") == "1":
+        return "REALHF_AMD_NO_FUSED_DECODE=1"
+    if model.pp_size > 1:
+        return "pp > 1 generation"
+    return None
+
+
+def effective_kv_quant(model: ReaLModel,
+                       gconfig: GenerationHyperparameters) -> str:
+    """resolve_kv_quant, downgraded to "none" (one logged warning per model)
+    where kv_quant_blocker names a reason."""
+    mode = resolve_kv_quant(gconfig)
+    if mode == "none":
+        return mode
+    why = kv_quant_blocker(model)
+    if why is None:
+        return mode
+    if not getattr(model, "_kv_quant_warned", False):
+        logger.warning("kv_quant=%s ignored for this model: %s; "
+                       "generating with %s KV caches", mode, why, model.dtype)
+        model._kv_quant_warned = True
+    return "none"
+
+
 class Fp8DecodeWeights:
     """One persistent (q, scale) pair per decode projection (merged QKV, wo,
     merged gate/up, down) of every local block.  A projection whose shape
@@ -249,7 +302,8 @@ class GenerationSession:
     """Persistent KV caches + captured decode graph, reused across generate
     calls of the same shape (the capture costs ~100 eager layer launches;
     re-capturing per call was ~2 s/step at the 7B bench shape).  With
-    weight_quant="fp8_e4m3" it also owns the quantized decode weights."""
+    weight_quant="fp8_e4m3" it also owns the quantized decode weights; with
+    kv_quant="fp8_e4m3" each kv_caches entry is a pair of ops.Fp8KVCache."""
 
     def __init__(self, kv_caches, decoder, fp8: Optional[Fp8DecodeWeights] = None):
         self.kv_caches = kv_caches
@@ -257,34 +311,46 @@ class GenerationSession:
         self.fp8 = fp8
 
 
-def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str):
-    """The quant mode is part of the key: the captured graph has the weight
-    format baked in (and, for fp8, whether the kernel or the
-    REALHF_AMD_NO_FP8_SKINNY reference reads it)."""
+def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str,
+                 kv_quant: str = "none"):
+    """The quant modes are part of the key: the captured graph has the
+    weight and cache formats baked in (and, for fp8, whether the kernels or
+    the REALHF_AMD_NO_FP8_SKINNY / REALHF_AMD_NO_FP8_KV references read
+    them)."""
     key = (bs, cache_len, id(model.flat_param), weight_quant)
     if weight_quant != "none":
         key += (ops.fp8_skinny_enabled(),)
+    if kv_quant != "none":
+        key += ("kv:" + kv_quant, ops.fp8_kv_enabled())
     return key
 
 
 def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device,
-                 weight_quant: str = "none"):
+                 weight_quant: str = "none", kv_quant: str = "none"):
     cfg = model.config
-    key = _session_key(model, bs, cache_len, weight_quant)
+    key = _session_key(model, bs, cache_len, weight_quant, kv_quant)
     sess = getattr(model, "_gen_session", None)
     if sess is not None and sess[0] == key:
         return sess[1]
     model._gen_session = None  # drop the old caches before allocating
     n_blocks = sum(1 for i in model.layer_indices if 1 <= i <= cfg.n_layers)
-    kv_caches = [
-        (
-            torch.zeros(bs, cache_len, nkv_local, cfg.head_dim,
-                        dtype=model.dtype, device=device),
-            torch.zeros(bs, cache_len, nkv_local, cfg.head_dim,
-                        dtype=model.dtype, device=device),
-        )
-        for _ in range(n_blocks)
-    ]
+    if kv_quant == "fp8_e4m3":
+        # (codes, scale) pairs, zeroed: code 0 decodes to 0
+        kv_caches = [
+            tuple(ops.Fp8KVCache.zeros(bs, cache_len, nkv_local, cfg.head_dim,
+                                       device) for _ in range(2))
+            for _ in range(n_blocks)
+        ]
+    else:
+        kv_caches = [
+            (
+                torch.zeros(bs, cache_len, nkv_local, cfg.head_dim,
+                            dtype=model.dtype, device=device),
+                torch.zeros(bs, cache_len, nkv_local, cfg.head_dim,
+                            dtype=model.dtype, device=device),
+            )
+            for _ in range(n_blocks)
+        ]
     fp8 = Fp8DecodeWeights(model) if weight_quant == "fp8_e4m3" else None
     s = GenerationSession(kv_caches, DecodeGraph(model, kv_caches, bs), fp8)
     model._gen_session = (key, s)
@@ -331,8 +397,10 @@ def generate(
     cache_len = ((max_prompt + max_new + 127) // 128) * 128
 
     weight_quant = effective_weight_quant(model, gconfig)
+    kv_quant = effective_kv_quant(model, gconfig)
     nkv_local = max(cfg.n_kv_heads // model.tp_size, 1)
-    sess = _get_session(model, bs, cache_len, nkv_local, device, weight_quant)
+    sess = _get_session(model, bs, cache_len, nkv_local, device, weight_quant,
+                        kv_quant)
     if sess.fp8 is None:
         return _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens,
                          max_prompt, gconfig, eos_token_id, pad_token_id,
@@ -398,6 +466,10 @@ def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
         and (cfg.moe is None
              or (cfg.moe.pad_to_capacity
                  and os.environ.get("REALHF_AMD_MOE_GRAPH") == "1"))
+        # an FP8 KV cache under REALHF_AMD_NO_FP8_KV=1 goes through the torch
+        # references, which read the lengths on the host: eager decode
+        and not (kv_caches and isinstance(kv_caches[0][0], ops.Fp8KVCache)
+                 and not ops.fp8_kv_enabled())
     )
 
     # logits-mask mode (force_no_logits_mask=False): record which vocab

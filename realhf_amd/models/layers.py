@@ -238,6 +238,9 @@ class ReaLModelBlock(nn.Module):
         # RoPE + KV append (HIP only, bf16, no qk-layernorm)
         import os as _os
 
+        # FP8 KV cache (generation's kv_quant="fp8_e4m3"): (codes, scale)
+        # pairs instead of bf16 tensors
+        fp8_kv = isinstance(k_cache, ops.Fp8KVCache)
         if (
             decode
             and h.is_cuda
@@ -276,10 +279,34 @@ class ReaLModelBlock(nn.Module):
                 scaling_type=cfg.rotary_scaling_type,
                 orig_max_pos=cfg.max_position_embeddings,
             )
-            q = C.rope_qkv_decode(
-                qkv_raw, bias, k_cache, v_cache,
-                cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
-            )
+            if fp8_kv and not ops.fp8_kv_enabled():
+                # REALHF_AMD_NO_FP8_KV=1, the A/B baseline and test oracle:
+                # the unchanged bf16 epilogue writes into scratch caches and
+                # the rows it wrote go through the reference quantizer, so
+                # the fp8 cache receives the rows the kernel below would
+                # have quantized; ops.attn_decode then takes the reference
+                ks, vs = (torch.empty(k_cache.shape, dtype=torch.bfloat16,
+                                      device=x.device) for _ in range(2))
+                q = C.rope_qkv_decode(
+                    qkv_raw, bias, ks, vs,
+                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
+                )
+                idx = (cache_seqlens.long() - 1).clamp(min=0)
+                b_idx = torch.arange(ks.shape[0], device=x.device)
+                ops.fp8_kv_append_ref(ks[b_idx, idx], vs[b_idx, idx],
+                                      k_cache, v_cache, cache_seqlens)
+            elif fp8_kv:
+                # the same epilogue, quantizing the K and V head rows
+                q = C.rope_qkv_decode_fp8(
+                    qkv_raw, bias, k_cache.codes, k_cache.scale,
+                    v_cache.codes, v_cache.scale,
+                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
+                )
+            else:
+                q = C.rope_qkv_decode(
+                    qkv_raw, bias, k_cache, v_cache,
+                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
+                )
             attn_out = ops.attn_decode(q, k_cache, v_cache, cache_seqlens,
                                        scale, window=cfg.sliding_window)
             attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
@@ -360,10 +387,13 @@ class ReaLModelBlock(nn.Module):
             # one new token per sequence; write into cache then attend
             bs = k_cache.shape[0]
             assert q.shape[0] == bs
-            idx = (cache_seqlens.long() - 1).clamp(min=0)
-            b_idx = torch.arange(bs, device=x.device)
-            k_cache[b_idx, idx] = k.to(k_cache.dtype)
-            v_cache[b_idx, idx] = v.to(v_cache.dtype)
+            if fp8_kv:
+                ops.fp8_kv_append_ref(k, v, k_cache, v_cache, cache_seqlens)
+            else:
+                idx = (cache_seqlens.long() - 1).clamp(min=0)
+                b_idx = torch.arange(bs, device=x.device)
+                k_cache[b_idx, idx] = k.to(k_cache.dtype)
+                v_cache[b_idx, idx] = v.to(v_cache.dtype)
             attn_out = ops.attn_decode(
                 q, k_cache, v_cache, cache_seqlens, scale,
                 window=cfg.sliding_window,
@@ -393,7 +423,12 @@ class ReaLModelBlock(nn.Module):
                 )
                 attn_out = cp_mod.head_gather_seq_scatter(attn_out)
             else:
-                if k_cache is not None:
+                if fp8_kv:
+                    # prefill into an FP8 cache: one quantizing store; the
+                    # attention below still sees the fresh bf16 K/V
+                    ops.fp8_kv_store(k, v, k_cache, v_cache, cu_seqlens,
+                                     positions)
+                elif k_cache is not None:
                     # prefill: write all tokens into the cache
                     bs = k_cache.shape[0]
                     seq_id = torch.bucketize(

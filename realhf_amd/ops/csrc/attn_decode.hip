@@ -16,8 +16,10 @@
 //   accumulated from LDS (conflict-free b32 reads), p broadcast by shfl.
 //   Wave partials (m, s, acc) combine through LDS at the end.
 #include "common.h"
+#include "fp8_e4m3.h"
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2q;
+typedef __attribute__((ext_vector_type(4))) int int4q;
 
 // Wave count trade-off: the per-wave V tile is W*64*HD*2 bytes of LDS —
 // at HD=128, W=8 needs 128 KB (ONE workgroup per CU: the PV phase has
@@ -37,13 +39,29 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2q;
 // softmax-combined by attn_decode_combine_kernel.  nsplit is chosen
 // from bs*nkv only (static for hipGraph capture); per-batch ranges are
 // derived in-kernel from the dynamic cache_seqlens.
-template <int HD, int REP, int W>
+//
+// FP8 = true reads the FP8 KV cache: kc / vc are e4m3 codes (one byte per
+// element, same [bs, maxlen, nkv, hd] layout) and kscale / vscale hold one
+// fp32 scale per (sequence, kv head, key) in [bs, nkv, maxlen], so lane =
+// key reads them contiguously.  The structure is the bf16 kernel's:
+//   K: hd bytes per key in 16-byte loads; v_cvt_pk_f32_fp8 decodes exactly
+//   and the upper halves are the bf16 pairs v_dot2 takes against the raw
+//   bf16 q_s; the key's scale multiplies the score once, with `scale`.
+//   V: the codes go to the LDS tile raw (half the bf16 tile); the key's
+//   v_scale is folded into the broadcast weight (pv = p * v_scale; the
+//   softmax sum keeps the unscaled p) and the PV loop decodes the lane's
+//   DPL codes from one LDS read.
+// A lane outside [lo, L) never loads its scales (they may be NaN, and
+// 0 * NaN is NaN) and zeroes its tile row (a stale byte can be a NaN code).
+template <int HD, int REP, int W, bool FP8 = false>
 __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
-    const bf16* __restrict__ q, const bf16* __restrict__ kc,
-    const bf16* __restrict__ vc, const int* __restrict__ cache_seqlens,
+    const bf16* __restrict__ q, const void* __restrict__ kc,
+    const void* __restrict__ vc, const float* __restrict__ kscale,
+    const float* __restrict__ vscale, const int* __restrict__ cache_seqlens,
     bf16* __restrict__ out, float* __restrict__ ws, int bs, int nq, int nkv,
     long maxlen, float scale, int window) {
   constexpr int DPL = HD / WAVE;  // dims per lane (2 for hd=128, 4 for 256)
+  using cache_t = std::conditional_t<FP8, unsigned char, __bf16>;
   const int b = blockIdx.x / nkv;
   const int kvh = blockIdx.x % nkv;
   const int nsplit = gridDim.y;
@@ -53,7 +71,8 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
   const int w = threadIdx.x / WAVE;
 
   __shared__ __bf16 q_s[REP][HD];  // raw bf16: K-dot uses v_dot2 pairs
-  __shared__ __bf16 v_s[W][WAVE][HD];  // per-wave V chunk tile
+  // per-wave V chunk tile (FP8: raw codes, written 16 bytes at a time)
+  __shared__ alignas(FP8 ? 16 : alignof(__bf16)) cache_t v_s[W][WAVE][HD];
   __shared__ float m_s[W], s_s[W];
   __shared__ float acc_s[W][HD];
 
@@ -73,8 +92,13 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
   }
 
   const long kv_stride = (long)nkv * HD;  // per-key stride
-  const bf16* kb = kc + (long)b * maxlen * kv_stride + (long)kvh * HD;
-  const bf16* vb = vc + (long)b * maxlen * kv_stride + (long)kvh * HD;
+  const cache_t* kb =
+      (const cache_t*)kc + (long)b * maxlen * kv_stride + (long)kvh * HD;
+  const cache_t* vb =
+      (const cache_t*)vc + (long)b * maxlen * kv_stride + (long)kvh * HD;
+  // FP8: this (sequence, kv head)'s per-key scales
+  const float* ksb = FP8 ? kscale + ((long)b * nkv + kvh) * maxlen : nullptr;
+  const float* vsb = FP8 ? vscale + ((long)b * nkv + kvh) * maxlen : nullptr;
 
   // sliding window (mistral): only keys in [L - window, L) attend
   const int lo = (window > 0 && L > window) ? (L - window) : 0;
@@ -95,13 +119,50 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
     if (!valid) {
       // windowed: front-invalid lanes are INSIDE the PV j-range, so
       // their V tile rows must be zeros (0 * uninitialized LDS = NaN)
+      if constexpr (FP8) {
+        #pragma unroll
+        for (int i = 0; i < HD / 16; i++)
+          *(int4q*)(&v_s[w][lane][i * 16]) = int4q{};
+      } else {
       #pragma unroll
       for (int i = 0; i < HD / 8; i++)
         *(short8*)(&v_s[w][lane][i * 8]) = short8{};
+      }
     }
+    float ks_l = scale, vs_l = 0.f;  // FP8: scale * k_scale[l], v_scale[l]
+    if constexpr (FP8) {
+      if (valid) {
+        ks_l = scale * ksb[l];
+        vs_l = vsb[l];
+        const cache_t* krow = kb + (long)l * kv_stride;
+        const cache_t* vrow = vb + (long)l * kv_stride;
+        #pragma unroll
+        for (int i = 0; i < HD / 16; i++) {
+          int4q k16 = *(const int4q*)(krow + i * 16);
+          int4q v16 = *(const int4q*)(vrow + i * 16);
+          *(int4q*)(&v_s[w][lane][i * 16]) = v16;
+          #pragma unroll
+          for (int c = 0; c < 4; c++) {
+            const float2v p0 = __builtin_amdgcn_cvt_pk_f32_fp8(k16[c], false);
+            const float2v p1 = __builtin_amdgcn_cvt_pk_f32_fp8(k16[c], true);
+            const unsigned k01 = bf16_pair_of(p0[0], p0[1]);
+            const unsigned k23 = bf16_pair_of(p1[0], p1[1]);
+            #pragma unroll
+            for (int r = 0; r < REP; r++) {
+              bf16x2q a0 = *(const bf16x2q*)(&q_s[r][i * 16 + c * 4]);
+              bf16x2q a1 = *(const bf16x2q*)(&q_s[r][i * 16 + c * 4 + 2]);
+              sc[r] = __builtin_amdgcn_fdot2_f32_bf16(
+                  a0, __builtin_bit_cast(bf16x2q, k01), sc[r], false);
+              sc[r] = __builtin_amdgcn_fdot2_f32_bf16(
+                  a1, __builtin_bit_cast(bf16x2q, k23), sc[r], false);
+            }
+          }
+        }
+      }
+    } else
     if (valid) {
-      const bf16* krow = kb + (long)l * kv_stride;
-      const bf16* vrow = vb + (long)l * kv_stride;
+      const bf16* krow = (const bf16*)kb + (long)l * kv_stride;
+      const bf16* vrow = (const bf16*)vb + (long)l * kv_stride;
       #pragma unroll
       for (int i = 0; i < HD / 8; i++) {
         short8 kv8 = *(const short8*)((const short*)krow + i * 8);
@@ -120,7 +181,7 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
       }
     }
     #pragma unroll
-    for (int r = 0; r < REP; r++) sc[r] *= scale;  // q kept raw bf16
+    for (int r = 0; r < REP; r++) sc[r] *= FP8 ? ks_l : scale;  // q kept raw bf16
     const int nvalid = min(WAVE, r1 - base);
     #pragma unroll
     for (int r = 0; r < REP; r++) {
@@ -136,8 +197,31 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
       s_w[r] += wave_sum(p);
       // role flip: lane owns DPL output dims; V comes from LDS,
       // p broadcast by shfl (no cross-wave LDS -> in-wave visibility)
+      // FP8: the key's v_scale rides on the broadcast weight
+      const float pv = FP8 ? (valid ? p * vs_l : 0.f) : p;
       for (int j = 0; j < nvalid; j++) {
-        float pj = __shfl(p, j, 64);
+        float pj = __shfl(pv, j, 64);
+        if constexpr (FP8) {
+          // one LDS read for the lane's DPL codes, decoded exactly
+          if constexpr (DPL == 1) {
+            const int u = v_s[w][j][lane];
+            acc_w[r][0] += pj * __builtin_amdgcn_cvt_f32_fp8(u, 0);
+          } else if constexpr (DPL == 2) {
+            const int u = *(const unsigned short*)(&v_s[w][j][lane * 2]);
+            const float2v f = __builtin_amdgcn_cvt_pk_f32_fp8(u, false);
+            acc_w[r][0] += pj * f[0];
+            acc_w[r][1] += pj * f[1];
+          } else {
+            static_assert(DPL == 4, "head_dim 64, 128 or 256");
+            const int u = *(const int*)(&v_s[w][j][lane * 4]);
+            const float2v f0 = __builtin_amdgcn_cvt_pk_f32_fp8(u, false);
+            const float2v f1 = __builtin_amdgcn_cvt_pk_f32_fp8(u, true);
+            acc_w[r][0] += pj * f0[0];
+            acc_w[r][1] += pj * f0[1];
+            acc_w[r][2] += pj * f1[0];
+            acc_w[r][3] += pj * f1[1];
+          }
+        } else
         if constexpr (DPL == 2) {
           // one b32 LDS read for the lane's two dims
           unsigned u = *(const unsigned*)(&v_s[w][j][lane * 2]);
@@ -226,9 +310,14 @@ __global__ __launch_bounds__(WAVE) void attn_decode_combine_kernel(
     out[head * HD + lane * DPL + d] = __float2bfloat16(o[d] * inv);
 }
 
-torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
-                          torch::Tensor cache_seqlens, double scale,
-                          long window) {
+// FP8: kc / vc are e4m3 codes and kscale / vscale their [bs, nkv, maxlen]
+// scales; else bf16 caches and null scales.  Wave count, split heuristic
+// and combine are the same for both.
+template <bool FP8>
+static torch::Tensor attn_decode_impl(
+    torch::Tensor q, torch::Tensor kc, torch::Tensor vc, const float* kscale,
+    const float* vscale, torch::Tensor cache_seqlens, double scale,
+    long window) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(q.is_contiguous() && kc.is_contiguous() && vc.is_contiguous());
   int bs = q.size(0), nq = q.size(1), hd = q.size(2);
@@ -264,11 +353,12 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   dim3 grid(bs * nkv, nsplit);
   auto launch = [&](auto hd_c, auto rep_c) {
     auto go = [&](auto w_c) {
-      hipLaunchKernelGGL((attn_decode_kernel<hd_c.value, rep_c.value, w_c.value>),
+      hipLaunchKernelGGL(
+        (attn_decode_kernel<hd_c.value, rep_c.value, w_c.value, FP8>),
         grid, dim3(64 * w_c.value), 0, cur_stream(), (const bf16*)q.data_ptr(),
-        (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-        cs.data_ptr<int>(), (bf16*)out.data_ptr(), ws_ptr, bs, nq, nkv, maxlen,
-        (float)scale, (int)window);
+        (const void*)kc.data_ptr(), (const void*)vc.data_ptr(), kscale, vscale,
+        (const int*)cs.data_ptr<int>(), (bf16*)out.data_ptr(), ws_ptr, bs, nq,
+        nkv, maxlen, (float)scale, (int)window);
       if (ws_ptr) {
         if (hd_c.value == 256)
           hipLaunchKernelGGL((attn_decode_combine_kernel<256>),
@@ -286,9 +376,16 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
     };
     if (dec_waves == 2) go(std::integral_constant<int, 2>{});
     else if (dec_waves == 8) {
-      // never reached at hd=256 (clamped above); not instantiated there
-      if constexpr (decltype(hd_c)::value != 256)
+      // never reached at hd=256 (clamped above); not instantiated there.
+      // FP8: under the 256-register cap of a 512-thread block the 8-wave
+      // kernels of rep 4 (hd 128) and rep 8 spill to scratch; they are not
+      // instantiated and the request runs with 4 waves
+      constexpr int hdv = decltype(hd_c)::value, repv = decltype(rep_c)::value;
+      if constexpr (hdv != 256 &&
+                    (!FP8 || repv <= 2 || (hdv == 64 && repv == 4)))
         go(std::integral_constant<int, 8>{});
+      else if constexpr (FP8)
+        go(std::integral_constant<int, 4>{});
     }
     else go(std::integral_constant<int, 4>{});
   };
@@ -307,4 +404,30 @@ torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   #undef REP_SWITCH
   CHECK_CUDA_OK();
   return out;
+}
+
+torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
+                          torch::Tensor cache_seqlens, double scale,
+                          long window) {
+  return attn_decode_impl<false>(q, kc, vc, nullptr, nullptr, cache_seqlens,
+                                 scale, window);
+}
+
+void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
+                        const char* what);  // rope_decode.hip
+
+torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
+                              torch::Tensor kscale, torch::Tensor vcodes,
+                              torch::Tensor vscale, torch::Tensor cache_seqlens,
+                              double scale, long window) {
+  check_fp8_kv_cache(kcodes, kscale, "k");
+  check_fp8_kv_cache(vcodes, vscale, "v");
+  TORCH_CHECK(kcodes.sizes() == vcodes.sizes());
+  TORCH_CHECK(q.dim() == 3 && q.size(0) == kcodes.size(0) &&
+              q.size(2) == kcodes.size(3) && q.size(1) % kcodes.size(2) == 0 &&
+              cache_seqlens.numel() == q.size(0),
+              "q [bs, nq, hd], the caches and cache_seqlens must agree");
+  return attn_decode_impl<true>(q, kcodes, vcodes, kscale.data_ptr<float>(),
+                                vscale.data_ptr<float>(), cache_seqlens, scale,
+                                window);
 }

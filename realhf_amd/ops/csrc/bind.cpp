@@ -92,6 +92,22 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor x, torch::Tensor q,
 torch::Tensor skinny_gemm_fp8_nc(torch::Tensor x, torch::Tensor q,
                                  torch::Tensor scale, torch::Tensor out32_ws,
                                  long splitk);
+// FP8 KV cache: e4m3 codes [bs, maxlen, nkv, hd] + fp32 scales
+// [bs, nkv, maxlen] for K and for V.  The quantizing decode append, the
+// quantizing prefill store and decode attention over the codes
+torch::Tensor rope_qkv_decode_fp8(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
+    torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope);
+void kv_store_fp8(torch::Tensor k, torch::Tensor v, torch::Tensor kcodes,
+                  torch::Tensor kscale, torch::Tensor vcodes,
+                  torch::Tensor vscale, torch::Tensor cu_seqlens,
+                  torch::Tensor positions);
+torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
+                              torch::Tensor kscale, torch::Tensor vcodes,
+                              torch::Tensor vscale, torch::Tensor cache_seqlens,
+                              double scale, long window);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -137,4 +153,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quantize_rows_e4m3_", &quantize_rows_e4m3_);
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
   m.def("skinny_gemm_fp8_nc", &skinny_gemm_fp8_nc);
+  m.def("rope_qkv_decode_fp8", &rope_qkv_decode_fp8);
+  m.def("kv_store_fp8", &kv_store_fp8);
+  m.def("attn_decode_fp8", &attn_decode_fp8);
 }

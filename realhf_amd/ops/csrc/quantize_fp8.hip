@@ -3,16 +3,16 @@
 //   amax     = max_k |float(w[n, k])|
 //   scale[n] = amax / 448 in fp32, or 1 when amax == 0
 //   q[n, k]  = rne_e4m3(float(w[n, k]) / scale[n]), clamped to +-448
-// The division is a true fp32 division (hipcc's default is the correctly
-// rounded one) and v_cvt_pk_fp8_f32 rounds to nearest even, so the result
-// is bit for bit what quantize_rows_e4m3_ref computes on the CPU.  The
-// clamp keeps every finite input off the NaN codes 0x7f / 0xff.  Rows with
+// The scale, the correctly rounded division, the clamp and the conversion
+// are fp8_e4m3.h's, shared with the FP8 KV cache writers: the result is bit
+// for bit what quantize_rows_e4m3_ref computes on the CPU.  Rows with
 // non-finite weights get no special handling.
 //
 // Shape follows rmsnorm.hip: one 256-thread workgroup per row, 16-byte
 // loads, the row read twice (amax pass, quantize pass; the second read hits
 // L2), wave reductions through LDS in a fixed order, no atomics.
 #include "common.h"
+#include "fp8_e4m3.h"
 
 #define QF8_THREADS 256
 
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(QF8_THREADS) void quantize_rows_e4m3_kernel(
   if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float s = amax == 0.f ? 1.f : amax / 448.f;
+  const float s = e4m3_row_scale(amax);
   if (threadIdx.x == 0) scale[row] = s;
 
   for (int i = threadIdx.x * VEC; i < K; i += QF8_THREADS * VEC) {
@@ -49,13 +49,10 @@ __global__ __launch_bounds__(QF8_THREADS) void quantize_rows_e4m3_kernel(
     float f[VEC];
     #pragma unroll
     for (int j = 0; j < VEC; j++)
-      f[j] = fminf(fmaxf(bf2f(v[j]) / s, -448.f), 448.f);
+      f[j] = e4m3_scaled(bf2f(v[j]), s);
     if constexpr (VEC == 8) {
-      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-      lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
-      hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-      int2 o = {lo, hi};
+      int2 o = {e4m3_pack4(f[0], f[1], f[2], f[3]),
+                e4m3_pack4(f[4], f[5], f[6], f[7])};
       *(int2*)(qr + i) = o;
     } else {
       qr[i] = (unsigned char)(

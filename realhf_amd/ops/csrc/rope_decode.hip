@@ -9,15 +9,26 @@
 // slabs [nks, bs, qkvd]; the per-element sum over nks happens in this
 // kernel's prologue (launch-boundary reduce) instead of a separate
 // sg_combine launch.
+//
+// FP8 mode (FP8 KV cache): the K and V head rows are not stored as bf16 but
+// quantized from the bf16-rounded values, per head row of hd elements, by
+// fp8_e4m3.h's definition: codes [bs, maxlen, nkv, hd] (one byte each) and
+// one fp32 scale per row in [bs, nkv, maxlen].  The hd/8 consecutive work
+// items of a head take its amax by shfl_xor.  That group is always inside
+// one wave and leaves the grid-stride loop together: the block is 256
+// threads, hd/8 is 8, 16 or 32, and nwork is a multiple of it.
 #include "common.h"
+#include "fp8_e4m3.h"
 
-template <bool SLAB>
+template <bool SLAB, int FP8_HD = 0>
 __global__ void rope_qkv_decode_kernel(
     const void* __restrict__ qkv_in,  // bf16 [bs, qkvd] | fp32 [nks, bs, qkvd]
     const bf16* __restrict__ bias,  // [(nq+2nkv)*hd] or null
     bf16* __restrict__ q_out,  // [bs, nq, hd]
-    bf16* __restrict__ kcache,  // [bs, maxlen, nkv, hd]
-    bf16* __restrict__ vcache,
+    void* __restrict__ kcache,  // [bs, maxlen, nkv, hd] bf16 | e4m3 codes
+    void* __restrict__ vcache,
+    float* __restrict__ kscale,  // FP8: [bs, nkv, maxlen], else unused
+    float* __restrict__ vscale,
     const int* __restrict__ cache_seqlens,  // [bs]
     const float* __restrict__ cosb, const float* __restrict__ sinb,  // [*, hd/2]
     int bs, int nq, int nkv, int hd, long maxlen, long qkv_stride,
@@ -71,9 +82,10 @@ __global__ void rope_qkv_decode_kernel(
     if (h < nq) {
       dst = q_out + ((long)b * nq + h) * hd;
     } else if (h < nq + nkv) {
-      dst = kcache + (((long)b * maxlen + pos) * nkv + (h - nq)) * hd;
+      dst = (bf16*)kcache + (((long)b * maxlen + pos) * nkv + (h - nq)) * hd;
     } else {
-      dst = vcache + (((long)b * maxlen + pos) * nkv + (h - nq - nkv)) * hd;
+      dst = (bf16*)vcache +
+            (((long)b * maxlen + pos) * nkv + (h - nq - nkv)) * hd;
       rope = false;
     }
     short o1[4], o2[4];
@@ -92,16 +104,45 @@ __global__ void rope_qkv_decode_kernel(
         ((bf16*)o2)[j] = __float2bfloat16(f2[j]);
       }
     }
+    if constexpr (FP8_HD != 0) {
+      if (h >= nq) {
+        // quantize the bf16-rounded head row: o1 / o2 hold what the bf16
+        // cache would have stored (dst is not used for these heads)
+        float amax = 0.f;
+        #pragma unroll
+        for (int j = 0; j < 4; j++)
+          amax = fmaxf(amax, fmaxf(fabsf(bf2f(o1[j])), fabsf(bf2f(o2[j]))));
+        amax = group_max<FP8_HD / 8>(amax);
+        const float sc = e4m3_row_scale(amax);
+        const bool is_k = h < nq + nkv;
+        const int kvh = is_k ? h - nq : h - nq - nkv;
+        unsigned char* cdst =
+            (unsigned char*)(is_k ? kcache : vcache) +
+            (((long)b * maxlen + pos) * nkv + kvh) * hd;
+        *(int*)(cdst + d0) = e4m3_pack4(
+            e4m3_scaled(bf2f(o1[0]), sc), e4m3_scaled(bf2f(o1[1]), sc),
+            e4m3_scaled(bf2f(o1[2]), sc), e4m3_scaled(bf2f(o1[3]), sc));
+        *(int*)(cdst + hd2 + d0) = e4m3_pack4(
+            e4m3_scaled(bf2f(o2[0]), sc), e4m3_scaled(bf2f(o2[1]), sc),
+            e4m3_scaled(bf2f(o2[2]), sc), e4m3_scaled(bf2f(o2[3]), sc));
+        if (quad == 0)
+          (is_k ? kscale : vscale)[((long)b * nkv + kvh) * maxlen + pos] = sc;
+        continue;
+      }
+    }
     *(short4v*)((short*)dst + d0) = *(short4v*)o1;
     *(short4v*)((short*)dst + hd2 + d0) = *(short4v*)o2;
   }
 }
 
-torch::Tensor rope_qkv_decode(
+// kscale / vscale null: bf16 caches; else e4m3 codes + fp32 row scales
+static torch::Tensor rope_qkv_decode_impl(
     torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
-    torch::Tensor vcache, torch::Tensor cache_seqlens, torch::Tensor cosb,
-    torch::Tensor sinb, long nq, bool apply_rope) {
+    torch::Tensor vcache, float* kscale, float* vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope) {
   TORCH_CHECK(qkv.is_cuda());
+  const bool fp8 = kscale != nullptr;
   const bool slab = qkv.dim() == 3;  // fp32 split-K partials [nks, bs, qkvd]
   if (slab) {
     TORCH_CHECK(qkv.scalar_type() == torch::kFloat && qkv.is_contiguous());
@@ -123,21 +164,69 @@ torch::Tensor rope_qkv_decode(
   const bf16* bptr = nullptr;
   if (bias.has_value()) bptr = (const bf16*)bias->data_ptr();
   long qkv_stride = slab ? qkv.stride(1) : qkv.stride(0);
-  if (slab) {
-    hipLaunchKernelGGL((rope_qkv_decode_kernel<true>), dim3(grid), dim3(256), 0,
-      cur_stream(), qkv.data_ptr(), bptr,
-      (bf16*)q_out.data_ptr(), (bf16*)kcache.data_ptr(),
-      (bf16*)vcache.data_ptr(), cache_seqlens.data_ptr<int>(),
-      cosb.data_ptr<float>(), sinb.data_ptr<float>(), bs, (int)nq, nkv, hd,
-      maxlen, qkv_stride, apply_rope, nks);
+  auto launch = [&](auto kern, int nks_arg) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, cur_stream(),
+      (const void*)qkv.data_ptr(), bptr, (bf16*)q_out.data_ptr(),
+      kcache.data_ptr(), vcache.data_ptr(), kscale, vscale,
+      (const int*)cache_seqlens.data_ptr<int>(),
+      (const float*)cosb.data_ptr<float>(), (const float*)sinb.data_ptr<float>(),
+      bs, (int)nq, nkv, hd, maxlen, qkv_stride, apply_rope, nks_arg);
+  };
+  if (!fp8) {
+    if (slab) launch(rope_qkv_decode_kernel<true>, nks);
+    else launch(rope_qkv_decode_kernel<false>, 1);
+  } else if (hd == 64) {
+    if (slab) launch(rope_qkv_decode_kernel<true, 64>, nks);
+    else launch(rope_qkv_decode_kernel<false, 64>, 1);
+  } else if (hd == 128) {
+    if (slab) launch(rope_qkv_decode_kernel<true, 128>, nks);
+    else launch(rope_qkv_decode_kernel<false, 128>, 1);
+  } else if (hd == 256) {
+    if (slab) launch(rope_qkv_decode_kernel<true, 256>, nks);
+    else launch(rope_qkv_decode_kernel<false, 256>, 1);
   } else {
-    hipLaunchKernelGGL((rope_qkv_decode_kernel<false>), dim3(grid), dim3(256), 0,
-      cur_stream(), qkv.data_ptr(), bptr,
-      (bf16*)q_out.data_ptr(), (bf16*)kcache.data_ptr(),
-      (bf16*)vcache.data_ptr(), cache_seqlens.data_ptr<int>(),
-      cosb.data_ptr<float>(), sinb.data_ptr<float>(), bs, (int)nq, nkv, hd,
-      maxlen, qkv_stride, apply_rope, 1);
+    TORCH_CHECK(false, "fp8 KV cache: unsupported head_dim ", hd);
   }
   CHECK_CUDA_OK();
   return q_out;
+}
+
+torch::Tensor rope_qkv_decode(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
+    torch::Tensor vcache, torch::Tensor cache_seqlens, torch::Tensor cosb,
+    torch::Tensor sinb, long nq, bool apply_rope) {
+  return rope_qkv_decode_impl(qkv, bias, kcache, vcache, nullptr, nullptr,
+                              cache_seqlens, cosb, sinb, nq, apply_rope);
+}
+
+// codes [bs, maxlen, nkv, hd] (one byte per element), scale fp32
+// [bs, nkv, maxlen]; everything else as rope_qkv_decode
+void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
+                        const char* what) {
+  TORCH_CHECK(codes.is_cuda() && codes.element_size() == 1 &&
+              codes.dim() == 4 && codes.is_contiguous(),
+              what, " codes must be contiguous [bs, maxlen, nkv, hd] with one "
+              "byte per element");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat32 &&
+              scale.dim() == 3 && scale.is_contiguous() &&
+              scale.size(0) == codes.size(0) && scale.size(1) == codes.size(2) &&
+              scale.size(2) == codes.size(1),
+              what, " scale must be contiguous fp32 [bs, nkv, maxlen]");
+}
+
+torch::Tensor rope_qkv_decode_fp8(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
+    torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope) {
+  check_fp8_kv_cache(kcodes, kscale, "k");
+  check_fp8_kv_cache(vcodes, vscale, "v");
+  TORCH_CHECK(kcodes.sizes() == vcodes.sizes());
+  const long bs = qkv.dim() == 3 ? qkv.size(1) : qkv.size(0);
+  TORCH_CHECK(bs == kcodes.size(0) && cache_seqlens.numel() == bs,
+              "batch size of qkv, caches and cache_seqlens must agree");
+  return rope_qkv_decode_impl(qkv, bias, kcodes, vcodes,
+                              kscale.data_ptr<float>(),
+                              vscale.data_ptr<float>(), cache_seqlens, cosb,
+                              sinb, nq, apply_rope);
 }

@@ -24,6 +24,12 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        skinny_linear_nc take the pair as fp8=(q, scale) and
                        stream q instead of the bf16 weight
                        (REALHF_AMD_NO_FP8_SKINNY=1: fp8_linear_ref instead)
+  Fp8KVCache         — e4m3 KV cache (codes + per-row fp32 scales):
+                       fp8_kv_store (quantizing prefill store), the fused
+                       decode block's rope_qkv_decode_fp8 append and
+                       attn_decode over the pair (attn_decode_fp8);
+                       REALHF_AMD_NO_FP8_KV=1 and the CPU take the
+                       fp8_kv_*_ref / attn_decode_fp8_ref torch forms
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -475,6 +481,20 @@ def attn_decode(q, k_cache, v_cache, cache_seqlens, softmax_scale=None,
     scale = softmax_scale or (1.0 / math.sqrt(q.shape[-1]))
     if window is not None and k_cache.shape[1] <= window:
         window = None  # cache can never exceed the window: plain causal
+    if isinstance(k_cache, Fp8KVCache):
+        if (
+            _ops.use_hip(q)
+            and fp8_kv_enabled()
+            and q.dtype == torch.bfloat16
+            and q.shape[-1] in HIP_ATTN_HEAD_DIMS
+            and q.shape[1] // k_cache.shape[2] in (1, 2, 4, 8)
+        ):
+            C = _ops.require_hip()
+            return C.attn_decode_fp8(q, k_cache.codes, k_cache.scale,
+                                     v_cache.codes, v_cache.scale,
+                                     cache_seqlens, scale, int(window or 0))
+        return attn_decode_fp8_ref(q, k_cache, v_cache, cache_seqlens, scale,
+                                   window=window)
     if (
         _ops.use_hip(q)
         and q.dtype == torch.bfloat16
@@ -876,6 +896,146 @@ def fp8_linear_ref(x: torch.Tensor, q: torch.Tensor, scale: torch.Tensor,
     if residual is not None:
         out = out + residual.float()
     return out.to(x.dtype)
+
+
+# ---------------------------------------------------------------------------
+# FP8 KV cache: e4m3 codes + one fp32 scale per head row
+# ---------------------------------------------------------------------------
+class Fp8KVCache:
+    """One layer's K (or V) cache in e4m3: codes [bs, maxlen, nkv, hd]
+    float8_e4m3fn and one fp32 scale per (sequence, kv head, position) laid
+    out [bs, nkv, maxlen] (the decode kernel's lane = key reads are
+    contiguous).  A row is quantize_rows_e4m3_ref of the hd bf16 values the
+    bf16 cache would hold.  .shape is the codes' shape, so callers that only
+    ask a cache for its sizes take either kind."""
+
+    __slots__ = ("codes", "scale")
+
+    def __init__(self, codes: torch.Tensor, scale: torch.Tensor):
+        bs, maxlen, nkv, _ = codes.shape
+        assert codes.dtype == torch.float8_e4m3fn
+        assert scale.dtype == torch.float32 and scale.shape == (bs, nkv, maxlen)
+        self.codes = codes
+        self.scale = scale
+
+    @classmethod
+    def zeros(cls, bs, maxlen, nkv, hd, device):
+        """Code 0 decodes to 0: a zeroed cache is an all-zero cache."""
+        return cls(
+            torch.zeros(bs, maxlen, nkv, hd, dtype=torch.uint8,
+                        device=device).view(torch.float8_e4m3fn),
+            torch.zeros(bs, nkv, maxlen, dtype=torch.float32, device=device),
+        )
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    def nbytes(self) -> int:
+        return self.codes.numel() + 4 * self.scale.numel()
+
+    def dequantize(self) -> torch.Tensor:
+        """fp32 [bs, maxlen, nkv, hd]"""
+        return self.codes.float() * self.scale.transpose(1, 2).unsqueeze(-1)
+
+
+def fp8_kv_enabled() -> bool:
+    """An FP8 KV cache is written and read by the HIP kernels unless
+    REALHF_AMD_NO_FP8_KV=1 (read at call time), which sends the same cache
+    through the torch references: the A/B baseline and the oracle of
+    tests/test_fp8_kv_gpu.py."""
+    return os.environ.get("REALHF_AMD_NO_FP8_KV") != "1"
+
+
+def _fp8_kv_put(cache: Fp8KVCache, x: torch.Tensor, seq: torch.Tensor,
+                pos: torch.Tensor):
+    """Quantize head rows x [n, nkv, hd] (from their bf16 rounding) into
+    cache at (seq[i], pos[i])."""
+    n, nkv, hd = x.shape
+    # quantize_rows_e4m3: the reference on the CPU; on the GPU the row
+    # quantizer kernel, which is bit for bit that reference (torch's own GPU
+    # division is not the correctly rounded one the definition asks for)
+    q, s = quantize_rows_e4m3(
+        x.detach().to(torch.bfloat16).reshape(-1, hd).contiguous())
+    # index_put on uint8 views: float8 tensors do not take it everywhere
+    cache.codes.view(torch.uint8)[seq, pos] = q.view(torch.uint8).reshape(n, nkv, hd)
+    cache.scale[seq, :, pos] = s.reshape(n, nkv)
+
+
+def fp8_kv_append_ref(k, v, k_cache: Fp8KVCache, v_cache: Fp8KVCache,
+                      cache_seqlens):
+    """Decode append: k / v [bs, nkv, hd] (K after RoPE) go to position
+    cache_seqlens - 1 of their sequence."""
+    idx = (cache_seqlens.long() - 1).clamp(min=0)
+    b_idx = torch.arange(k.shape[0], device=k.device)
+    _fp8_kv_put(k_cache, k, b_idx, idx)
+    _fp8_kv_put(v_cache, v, b_idx, idx)
+
+
+def fp8_kv_store_ref(k, v, k_cache: Fp8KVCache, v_cache: Fp8KVCache,
+                     cu_seqlens, positions):
+    """Prefill store: packed k / v [total, nkv, hd] go to (sequence of the
+    token, positions[token])."""
+    seq_id = torch.bucketize(
+        torch.arange(k.shape[0], device=k.device), cu_seqlens[1:].long(),
+        right=True,
+    )
+    _fp8_kv_put(k_cache, k, seq_id, positions.long())
+    _fp8_kv_put(v_cache, v, seq_id, positions.long())
+
+
+def fp8_kv_store(k, v, k_cache: Fp8KVCache, v_cache: Fp8KVCache, cu_seqlens,
+                 positions):
+    """Quantizing prefill store: one HIP kernel for bf16 K/V on the GPU, the
+    reference elsewhere and under REALHF_AMD_NO_FP8_KV=1."""
+    if (
+        _ops.use_hip(k)
+        and fp8_kv_enabled()
+        and k.dtype == torch.bfloat16
+        and k.shape[-1] in HIP_ATTN_HEAD_DIMS
+    ):
+        C = _ops.require_hip()
+
+        def rows(x):  # [total, nkv, hd] views into the QKV projection pass
+            x = x.detach()
+            ok = (x.stride(2) == 1
+                  and (x.shape[1] == 1 or x.stride(1) == x.shape[2])
+                  and (x.shape[0] <= 1 or x.stride(0) % 8 == 0)
+                  and x.data_ptr() % 16 == 0)
+            return x if ok else x.contiguous()
+
+        C.kv_store_fp8(rows(k), rows(v), k_cache.codes, k_cache.scale,
+                       v_cache.codes, v_cache.scale,
+                       cu_seqlens.to(torch.int32).contiguous(),
+                       positions.long().contiguous())
+        return
+    fp8_kv_store_ref(k, v, k_cache, v_cache, cu_seqlens, positions)
+
+
+def attn_decode_fp8_ref(q, k_cache: Fp8KVCache, v_cache: Fp8KVCache,
+                        cache_seqlens, softmax_scale=None, window=None):
+    """attn_decode_ref in fp32 on the dequantized caches, returned in
+    q.dtype.  Only the attended positions [lo, L) are dequantized, so
+    whatever lies outside them (stale or non-finite) never enters."""
+    bs, nq, hd = q.shape
+    scale = softmax_scale or (1.0 / math.sqrt(hd))
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    for b in range(bs):
+        L = int(cache_seqlens[b])
+        lo = max(0, L - window) if window is not None else 0
+
+        def deq(c):
+            x = c.codes[b:b + 1, lo:L].float()
+            return x * c.scale[b:b + 1, :, lo:L].transpose(1, 2).unsqueeze(-1)
+
+        out[b] = attn_decode_ref(
+            q[b:b + 1].float(), deq(k_cache), deq(v_cache),
+            torch.tensor([L - lo]), scale)[0]
+    return out.to(q.dtype)
 
 
 # ---------------------------------------------------------------------------

@@ -302,6 +302,8 @@ class PipelinedEngine(PipelinableEngine):
         # FP8 weight-only decode belongs to the pp == 1 session: validated
         # here, then ignored with one warning (bf16 weights)
         genmod.effective_weight_quant(self.model, gconfig)
+        # the FP8 KV cache likewise (the stage caches here stay bf16)
+        genmod.effective_kv_quant(self.model, gconfig)
         cfg = self.model.config
         dev = self.model.flat_param.device
         dtype = self.model.dtype

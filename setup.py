@@ -28,6 +28,7 @@ SRC = [
     "realhf_amd/ops/csrc/attn_bwd.hip",
     "realhf_amd/ops/csrc/logprob.hip",
     "realhf_amd/ops/csrc/quantize_fp8.hip",
+    "realhf_amd/ops/csrc/kv_store_fp8.hip",
 ]
 
 setup(
