@@ -24,7 +24,7 @@ import torch
 
 from realhf_amd.api.model import GenerationHyperparameters
 from realhf_amd.base import logging
-from realhf_amd.models.layers import ReaLModelBlock
+from realhf_amd.models.layers import ReaLModelBlock, fused_decode_blocker
 from realhf_amd.models.real_model import ReaLModel
 from realhf_amd.ops import functional as ops
 from realhf_amd.utils.functional import top_k_top_p_logits  # noqa: F401 — re-exported for interface use
@@ -114,8 +114,6 @@ class DecodeGraph:
         )
 
     def capture(self, tokens, cache_seqlens):
-        import os
-
         if os.environ.get("REALHF_AMD_FORCE_GRAPH_FAIL") == "1":
             # test hook: exercise the eager fallback path (a capture can
             # fail for real when the forward contains a graph-unsafe op,
@@ -149,109 +147,97 @@ class DecodeGraph:
 
 
 WEIGHT_QUANT_MODES = ("none", "fp8_e4m3")
+KV_QUANT_MODES = ("none", "fp8_e4m3")
+
+
+def _resolve_quant(gconfig, field: str, env: str, modes) -> str:
+    """The requested mode: the gconfig field when set, else the environment
+    variable read now (default "none")."""
+    mode = getattr(gconfig, field)
+    if mode is None:
+        mode = os.environ.get(env) or "none"
+    if mode not in modes:
+        raise ValueError(
+            f"{field} must be one of {modes} or None, got {mode!r}")
+    return mode
+
+
+def _quant_blocker(model: ReaLModel, dtype) -> Optional[str]:
+    """Why the fused decode block would not run this model's decode steps on
+    the GPU in `dtype` (layers.fused_decode_blocker, the one gate), then
+    pp > 1 generation, which does not go through a session."""
+    why = fused_decode_blocker(model.config, dtype, True,
+                               getattr(model, "lora_flat", None) is not None)
+    if why is None and model.pp_size > 1:
+        why = "pp > 1 generation"
+    return why
+
+
+def _effective_quant(model, mode: str, field: str, blocker, warned: str,
+                     consequence: str) -> str:
+    """mode, downgraded to "none" (one logged warning per model, remembered
+    in the attribute `warned`) where blocker(model) names a reason."""
+    if mode == "none":
+        return mode
+    why = blocker(model)
+    if why is None:
+        return mode
+    if not getattr(model, warned, False):
+        logger.warning("%s=%s ignored for this model: %s; %s", field, mode,
+                       why, consequence)
+        setattr(model, warned, True)
+    return "none"
 
 
 def resolve_weight_quant(gconfig: GenerationHyperparameters) -> str:
-    """The requested decode weight format: the gconfig field when set, else
-    REALHF_AMD_GEN_WEIGHT_QUANT read now (default "none")."""
-    mode = gconfig.weight_quant
-    if mode is None:
-        mode = os.environ.get("REALHF_AMD_GEN_WEIGHT_QUANT") or "none"
-    if mode not in WEIGHT_QUANT_MODES:
-        raise ValueError(
-            f"weight_quant must be one of {WEIGHT_QUANT_MODES} or None, "
-            f"got {mode!r}")
-    return mode
+    """The requested decode weight format (REALHF_AMD_GEN_WEIGHT_QUANT when
+    the field is None)."""
+    return _resolve_quant(gconfig, "weight_quant",
+                          "REALHF_AMD_GEN_WEIGHT_QUANT", WEIGHT_QUANT_MODES)
 
 
 def weight_quant_blocker(model: ReaLModel) -> Optional[str]:
     """Why FP8 weight-only decode cannot be used with this model (None if it
-    can): every case in which the fused decode block, the only reader of
-    the quantized weights on the GPU, is not what runs."""
-    cfg = model.config
-    if getattr(model, "lora_flat", None) is not None:
-        return "LoRA adapters are attached"
-    if cfg.qk_layernorm:
-        return "qk_layernorm"
-    if cfg.head_dim not in ops.HIP_ATTN_HEAD_DIMS:
-        return f"head_dim {cfg.head_dim} not in {ops.HIP_ATTN_HEAD_DIMS}"
-    if model.dtype != torch.bfloat16:
-        return f"model dtype {model.dtype} is not bfloat16"
-    if os.environ.get("REALHF_AMD_NO_FUSED_DECODE") == "1":
-        return "REALHF_AMD_NO_FUSED_DECODE=1"
-    if model.pp_size > 1:
-        return "pp > 1 generation"
-    return None
+    can): every case in which the fused decode block, the only reader of the
+    quantized weights on the GPU, is not what runs.  A non-bf16 model is
+    blocked on any device."""
+    return _quant_blocker(model, model.dtype)
 
 
 def effective_weight_quant(model: ReaLModel,
                            gconfig: GenerationHyperparameters) -> str:
     """resolve_weight_quant, downgraded to "none" (one logged warning per
     model) where weight_quant_blocker names a reason."""
-    mode = resolve_weight_quant(gconfig)
-    if mode == "none":
-        return mode
-    why = weight_quant_blocker(model)
-    if why is None:
-        return mode
-    if not getattr(model, "_weight_quant_warned", False):
-        logger.warning("weight_quant=%s ignored for this model: %s; "
-                       "decoding with bf16 weights", mode, why)
-        model._weight_quant_warned = True
-    return "none"
-
-
-KV_QUANT_MODES = ("none", "fp8_e4m3")
+    return _effective_quant(
+        model, resolve_weight_quant(gconfig), "weight_quant",
+        weight_quant_blocker, "_weight_quant_warned",
+        "decoding with bf16 weights")
 
 
 def resolve_kv_quant(gconfig: GenerationHyperparameters) -> str:
-    """The requested KV cache format: the gconfig field when set, else
-    REALHF_AMD_GEN_KV_QUANT read now (default "none")."""
-    mode = gconfig.kv_quant
-    if mode is None:
-        mode = os.environ.get("REALHF_AMD_GEN_KV_QUANT") or "none"
-    if mode not in KV_QUANT_MODES:
-        raise ValueError(
-            f"kv_quant must be one of {KV_QUANT_MODES} or None, got {mode!r}")
-    return mode
+    """The requested KV cache format (REALHF_AMD_GEN_KV_QUANT when the field
+    is None)."""
+    return _resolve_quant(gconfig, "kv_quant", "REALHF_AMD_GEN_KV_QUANT",
+                          KV_QUANT_MODES)
 
 
 def kv_quant_blocker(model: ReaLModel) -> Optional[str]:
     """Why the FP8 KV cache cannot be used with this model (None if it can).
     On the GPU the fused decode block is the only writer of the quantized
     cache, so weight_quant_blocker's cases apply; on the CPU the torch
-    references write and read it and any model dtype is fine."""
-    cfg = model.config
-    if getattr(model, "lora_flat", None) is not None:
-        return "LoRA adapters are attached"
-    if cfg.qk_layernorm:
-        return "qk_layernorm"
-    if cfg.head_dim not in ops.HIP_ATTN_HEAD_DIMS:
-        return f"head_dim {cfg.head_dim} not in {ops.HIP_ATTN_HEAD_DIMS}"
-    if model.flat_param.is_cuda and model.dtype != torch.bfloat16:
-        return f"model dtype {model.dtype} on the GPU is not bfloat16"
-    if os.environ.get("REALHF_AMD_NO_FUSED_DECODE") == "1":
-        return "REALHF_AMD_NO_FUSED_DECODE=1"
-    if model.pp_size > 1:
-        return "pp > 1 generation"
-    return None
+    references write and read it, so the model's dtype does not matter
+    there (the gate is asked as for bf16) while the other cases still do."""
+    return _quant_blocker(
+        model, model.dtype if model.flat_param.is_cuda else torch.bfloat16)
 
 
 def effective_kv_quant(model: ReaLModel,
                        gconfig: GenerationHyperparameters) -> str:
     """resolve_kv_quant, downgraded to "none" (one logged warning per model)
     where kv_quant_blocker names a reason."""
-    mode = resolve_kv_quant(gconfig)
-    if mode == "none":
-        return mode
-    why = kv_quant_blocker(model)
-    if why is None:
-        return mode
-    if not getattr(model, "_kv_quant_warned", False):
-        logger.warning("kv_quant=%s ignored for this model: %s; "
-                       "generating with %s KV caches", mode, why, model.dtype)
-        model._kv_quant_warned = True
-    return "none"
+    return _effective_quant(
+        model, resolve_kv_quant(gconfig), "kv_quant", kv_quant_blocker,
+        "_kv_quant_warned", f"generating with {model.dtype} KV caches")
 
 
 class Fp8DecodeWeights:
@@ -361,11 +347,7 @@ def decode_graph_supported(cfg, dtype, device) -> bool:
     """Whether the dense decode step runs fully on HIP kernels, which is
     what hipGraph capture needs: the torch fallback for other head dims or
     dtypes reads cache_seqlens on the host."""
-    return (
-        torch.device(device).type == "cuda"
-        and dtype == torch.bfloat16
-        and cfg.head_dim in ops.HIP_ATTN_HEAD_DIMS
-    )
+    return ops.hip_attn_supported(dtype, cfg.head_dim, device)
 
 
 @torch.no_grad()

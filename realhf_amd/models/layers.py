@@ -14,9 +14,16 @@ MI355X specifics: wq/wk/wv (and gate/up) flat regions are adjacent, so the
 module runs ONE hipBLASLt GEMM over the concatenated view; RMSNorm (plain
 and gemma's 1 + w) / RoPE / SwiGLU / GeGLU / attention are the hand-written
 HIP kernels in realhf_amd.ops.
+
+ReaLModelBlock.forward dispatches over three routes: training/prefill and
+eager decode attention, which share the wo + MLP epilogue, and the fused
+decode block, which runs exactly when fused_decode_blocker() names no reason
+(generation's quant blockers are built on the same function).  Every decode
+projection goes down one ladder, _decode_linear().
 """
 import math
-from typing import Dict, Optional
+import os
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -25,6 +32,8 @@ import torch.nn.functional as F
 from realhf_amd.api.model import ReaLModelConfig
 from realhf_amd.base import constants
 from realhf_amd.ops import functional as ops
+from realhf_amd.ops import require_hip
+from realhf_amd.parallel import cp as cp_mod
 from realhf_amd.parallel import mappings
 
 
@@ -53,6 +62,45 @@ def _maybe_merged(params: Dict[str, torch.Tensor], names, dim_out_total):
 
 def _linear(x, w, b=None):
     return F.linear(x, w, b)
+
+
+def _decode_linear(x, w, fp8=None, slabs=False,
+                   residual=None) -> Tuple[torch.Tensor, str]:
+    """The decode step's projection ladder for x @ w^T, fp8 = the block's
+    (q, scale) pair of w if it has one.  Returns (result, kind): "slabs",
+    ops.skinny_linear_nc's split-K partials, tried only if the caller's next
+    kernel sums them (slabs=True); "folded", ops.maybe_skinny_linear with
+    `residual` added in its combine; "plain", the same without a residual
+    or the dense GEMM, which leaves a residual to the caller.  Outside a
+    decode step (grad enabled, M > 16, CPU) a pair-less call is that GEMM."""
+    if slabs:
+        parts = ops.skinny_linear_nc(x, w, fp8=fp8)
+        if parts is not None:
+            return parts, "slabs"
+    out = ops.maybe_skinny_linear(x, w, residual=residual, fp8=fp8)
+    if out is None:
+        return _linear(x, w), "plain"
+    return out, "plain" if residual is None else "folded"
+
+
+def fused_decode_blocker(cfg: ReaLModelConfig, dtype, is_cuda: bool,
+                         has_lora: bool) -> Optional[str]:
+    """Why a decode step does not run the fused decode block (None if it
+    does).  The one gate: ReaLModelBlock.forward asks with its run-time
+    values, generation's weight_quant / kv_quant blockers for the model."""
+    if has_lora:  # adapters are applied in the eager route
+        return "LoRA adapters are attached"
+    if cfg.qk_layernorm:
+        return "qk_layernorm"
+    if cfg.head_dim not in ops.HIP_ATTN_HEAD_DIMS:
+        return f"head_dim {cfg.head_dim} not in {ops.HIP_ATTN_HEAD_DIMS}"
+    if dtype != torch.bfloat16:
+        return f"model dtype {dtype} is not bfloat16"
+    if os.environ.get("REALHF_AMD_NO_FUSED_DECODE") == "1":
+        return "REALHF_AMD_NO_FUSED_DECODE=1"
+    if not is_cuda:
+        return "the model is not on the GPU"
+    return None
 
 
 class VocabEmbedding(nn.Module):
@@ -172,13 +220,12 @@ class ReaLModelBlock(nn.Module):
             # forward and overlaps the bwd grad collective with the
             # weight-grad GEMM (mappings._ColumnParallelLinear)
             qkv = mappings.column_parallel_linear(x, merged, fused_sp)
-        elif fused_sp is not None:
-            x = (mappings.gather_from_sp_region(x) if fused_sp
-                 else mappings.copy_to_tp_region(x))
-            qkv = torch.cat([_linear(x, self.p[n]) for n in self._qkv_names], dim=-1)
         elif merged is not None:
             qkv = _linear(x, merged)
         else:
+            if fused_sp is not None:
+                x = (mappings.gather_from_sp_region(x) if fused_sp
+                     else mappings.copy_to_tp_region(x))
             qkv = torch.cat([_linear(x, self.p[n]) for n in self._qkv_names], dim=-1)
         i = self.i
         if f"{i}.attn.wq.bias" in self.p:
@@ -214,10 +261,12 @@ class ReaLModelBlock(nn.Module):
         cache_seqlens: Optional[torch.Tensor] = None,  # [bs]
         decode: bool = False,
     ):
+        """Shared prologue (attention norm, SP/TP input mapping, scale), then
+        one route: training/prefill attention, the fused decode block where
+        fused_decode_blocker names no reason, else eager decode attention.
+        A cache is a bf16 tensor or (kv_quant="fp8_e4m3") an ops.Fp8KVCache."""
         i = self.i
         cfg = self.cfg
-        # prefill and training never read the quantized weights
-        fp8 = self.fp8 if decode else {}
         h = _norm(cfg, x, self.p[f"{i}.attn.ln.weight"], self.p.get(f"{i}.attn.ln.bias"))
         sp = constants.has_current() and constants.sequence_parallel()
         # fused column linear (async bwd comm) takes the PRE-mapping h;
@@ -225,323 +274,274 @@ class ReaLModelBlock(nn.Module):
         fused_col = (self.tp_size > 1 and torch.is_grad_enabled()
                      and not self.lora and not decode)
         if not fused_col:
-            if sp:
-                h = mappings.gather_from_sp_region(h)
-            else:
-                h = mappings.copy_to_tp_region(h)
+            h = (mappings.gather_from_sp_region(h) if sp
+                 else mappings.copy_to_tp_region(h))
 
         scale = 1.0 / math.sqrt(self.hd)
         if cfg.scale_attn_by_inverse_layer_idx:
             scale = scale / float(self.i)
 
-        # ---- fused decode fast path: one kernel for qkv-split + bias +
-        # RoPE + KV append (HIP only, bf16, no qk-layernorm)
-        import os as _os
+        if not decode:
+            attn_out = self._prefill_attn(
+                h, sp if fused_col else None, scale, cu_seqlens, max_seqlen,
+                positions, k_cache, v_cache)
+        elif fused_decode_blocker(cfg, h.dtype, h.is_cuda,
+                                  bool(self.lora)) is None:
+            return self._fused_decode(x, h, sp, scale, k_cache, v_cache,
+                                      cache_seqlens)
+        else:
+            attn_out = self._decode_attn(h, scale, positions, k_cache,
+                                         v_cache, cache_seqlens)
+        # prefill and training never read the quantized weights
+        return self._attn_epilogue(x, attn_out, sp,
+                                   self.fp8 if decode else {})
 
-        # FP8 KV cache (generation's kv_quant="fp8_e4m3"): (codes, scale)
-        # pairs instead of bf16 tensors
-        fp8_kv = isinstance(k_cache, ops.Fp8KVCache)
-        if (
-            decode
-            and h.is_cuda
-            and h.dtype == torch.bfloat16
-            and not cfg.qk_layernorm
-            and self.hd in ops.HIP_ATTN_HEAD_DIMS
-            and _os.environ.get("REALHF_AMD_NO_FUSED_DECODE") != "1"
-            and not self.lora  # adapters applied in the standard path
-        ):
-            from realhf_amd import ops as _ops_pkg
+    def _rope_tables(self, rot_len: int, device):
+        cfg = self.cfg
+        return ops.rotary_cache.get(
+            self.hd, rot_len, cfg.rotary_base, device,
+            scaling=cfg.rotary_scaling,
+            scaling_type=cfg.rotary_scaling_type,
+            orig_max_pos=cfg.max_position_embeddings,
+        )
 
-            C = _ops_pkg.require_hip()
-            qkv_dim = (self.nq + 2 * self.nkv) * self.hd
-            merged = _maybe_merged(self.p, self._qkv_names, qkv_dim)
-            if merged is not None:
-                # launch-boundary reduce: hand the split-K fp32 slabs
-                # straight to rope_qkv_decode's prologue (no combine pass)
-                qkv_raw = ops.skinny_linear_nc(h, merged, fp8=fp8.get("qkv"))
-                if qkv_raw is None:
-                    qkv_raw = ops.maybe_skinny_linear(h, merged,
-                                                      fp8=fp8.get("qkv"))
-                if qkv_raw is None:
-                    qkv_raw = _linear(h, merged)
-            else:
-                qkv_raw = torch.cat(
-                    [_linear(h, self.p[n]) for n in self._qkv_names], dim=-1
-                )
-            bias = None
-            if f"{i}.attn.wq.bias" in self.p:
-                bias = torch.cat(
-                    [self.p[f"{i}.attn.w{c}.bias"] for c in "qkv"], dim=0
-                ).to(qkv_raw.dtype)
-            cos, sin = ops.rotary_cache.get(
-                self.hd, int(k_cache.shape[1]), cfg.rotary_base, x.device,
-                scaling=cfg.rotary_scaling,
-                scaling_type=cfg.rotary_scaling_type,
-                orig_max_pos=cfg.max_position_embeddings,
-            )
-            if fp8_kv and not ops.fp8_kv_enabled():
-                # REALHF_AMD_NO_FP8_KV=1, the A/B baseline and test oracle:
-                # the unchanged bf16 epilogue writes into scratch caches and
-                # the rows it wrote go through the reference quantizer, so
-                # the fp8 cache receives the rows the kernel below would
-                # have quantized; ops.attn_decode then takes the reference
-                ks, vs = (torch.empty(k_cache.shape, dtype=torch.bfloat16,
-                                      device=x.device) for _ in range(2))
-                q = C.rope_qkv_decode(
-                    qkv_raw, bias, ks, vs,
-                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
-                )
-                idx = (cache_seqlens.long() - 1).clamp(min=0)
-                b_idx = torch.arange(ks.shape[0], device=x.device)
-                ops.fp8_kv_append_ref(ks[b_idx, idx], vs[b_idx, idx],
-                                      k_cache, v_cache, cache_seqlens)
-            elif fp8_kv:
-                # the same epilogue, quantizing the K and V head rows
-                q = C.rope_qkv_decode_fp8(
-                    qkv_raw, bias, k_cache.codes, k_cache.scale,
-                    v_cache.codes, v_cache.scale,
-                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
-                )
-            else:
-                q = C.rope_qkv_decode(
-                    qkv_raw, bias, k_cache, v_cache,
-                    cache_seqlens, cos, sin, self.nq, cfg.apply_rotary,
-                )
-            attn_out = ops.attn_decode(q, k_cache, v_cache, cache_seqlens,
-                                       scale, window=cfg.sliding_window)
-            attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
-            wo = self.p[f"{i}.attn.wo.weight"]
-            # fused (x + o) + mlp-norm: plain RMS, or gemma's 1 + w mode
-            add_norm = None
-            if self.moe is not None:
-                pass
-            elif cfg.norm_type == "rms":
-                add_norm = C.add_rmsnorm_fwd
-            elif cfg.norm_type == "gemma_rms" and ops.gemma_ops_enabled():
-                add_norm = C.gemma_add_rmsnorm_fwd
-            if (
-                self.tp_size == 1
-                and f"{i}.attn.wo.bias" not in self.p
-                and add_norm is not None
-            ):
-                # launch-boundary reduce: o's split-K slabs are summed in
-                # the fused add+rmsnorm prologue (no combine, no bf16 o)
-                o_parts = ops.skinny_linear_nc(attn_out, wo, fp8=fp8.get("wo"))
-                if o_parts is not None:
-                    h2, x2 = add_norm(
-                        o_parts, x, self.p[f"{i}.mlp.ln.weight"],
-                        cfg.layer_norm_epsilon,
-                    )
-                    return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
-            o = ops.maybe_skinny_linear(attn_out, wo, fp8=fp8.get("wo"))
-            if o is None:
-                o = _linear(attn_out, wo)
-            o = mappings.reduce_from_tp_region(o)
-            if f"{i}.attn.wo.bias" in self.p:
-                o = o + self.p[f"{i}.attn.wo.bias"]
-            if add_norm is not None:
-                # fused (x + o) + mlp-norm, then the MLP body (the down
-                # projection folds the x2 residual into its combine)
-                h2, x2 = add_norm(
-                    o, x, self.p[f"{i}.mlp.ln.weight"], cfg.layer_norm_epsilon
-                )
-                return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
-            x = x + o
-            return self._mlp(x, sp, fp8=fp8)
+    def _rope(self, q, k, rot_len: int, positions):
+        cos, sin = self._rope_tables(rot_len, q.device)
+        interleaved = self.cfg.rotary_interleaved
+        return (ops.apply_rotary(q, cos, sin, positions, interleaved),
+                ops.apply_rotary(k, cos, sin, positions, interleaved))
 
-        q, k, v = self._qkv(h, fused_sp=(sp if fused_col else None),
-                            fp8=fp8.get("qkv"))
+    def _prefill_attn(self, h, fused_sp, scale, cu_seqlens, max_seqlen,
+                      positions, k_cache, v_cache):
+        """Training and generation prefill: packed varlen attention (through
+        the CP all-to-all route under context parallelism), writing the
+        prompt K/V into the caches when there are any."""
+        cfg = self.cfg
+        q, k, v = self._qkv(h, fused_sp=fused_sp)
         if cfg.apply_rotary:
             # graph-capture-safe length bound: never read positions back
-            if decode:
-                rot_len = int(k_cache.shape[1])
-            elif k_cache is not None:
+            if k_cache is not None:
                 # generation prefill: use the SESSION's cache length so
                 # dynamic-NTK picks one base for prefill AND decode (a
                 # per-length base would rotate cached K with a different
                 # basis than the decode queries reading it)
-                rot_len = max(int(k_cache.shape[1]),
-                              cfg.max_position_embeddings)
-            else:
-                ms = max_seqlen
-                if ms is None:  # CP: token shard with explicit positions
-                    from realhf_amd.parallel import cp as cp_mod
+                ms = int(k_cache.shape[1])
+            elif max_seqlen is not None:
+                ms = int(max_seqlen)
+            else:  # CP: token shard with explicit positions
+                c = cp_mod.current()
+                ms = int(c.info.full_max if c is not None
+                         else cfg.max_position_embeddings)
+            q, k = self._rope(q, k, max(ms, cfg.max_position_embeddings),
+                              positions)
 
-                    c = cp_mod.current()
-                    ms = (c.info.full_max if c is not None
-                          else cfg.max_position_embeddings)
-                rot_len = max(int(ms), cfg.max_position_embeddings)
-            cos, sin = ops.rotary_cache.get(
-                self.hd,
-                rot_len,
-                cfg.rotary_base,
-                x.device,
-                scaling=cfg.rotary_scaling,
-                scaling_type=cfg.rotary_scaling_type,
-                orig_max_pos=cfg.max_position_embeddings,
-            )
-            q = ops.apply_rotary(q, cos, sin, positions, cfg.rotary_interleaved)
-            k = ops.apply_rotary(k, cos, sin, positions, cfg.rotary_interleaved)
+        cpctx = cp_mod.current()
+        if cpctx is not None:
+            # Ulysses context parallelism: tokens are sharded over the CP
+            # group; one all-to-all gives this rank ALL tokens for 1/cp of
+            # the heads, the varlen kernel runs on full sequences, and a
+            # second all-to-all restores the (token-shard, all-heads)
+            # layout (parallel/cp.py).
+            assert k_cache is None, "CP: no KV-cache prefill/generation"
+            assert q.shape[1] % cpctx.size == 0, (
+                f"q heads {q.shape[1]} not divisible by cp {cpctx.size}")
+            assert k.shape[1] % cpctx.size == 0, (
+                f"kv heads {k.shape[1]} not divisible by cp {cpctx.size}")
+            q = cp_mod.seq_gather_head_scatter(q)
+            k = cp_mod.seq_gather_head_scatter(k)
+            v = cp_mod.seq_gather_head_scatter(v)
+            attn_out = ops.attn_varlen(
+                q, k, v, cpctx.info.full_cu, cpctx.info.full_max,
+                causal=True, softmax_scale=scale, window=cfg.sliding_window)
+            return cp_mod.head_gather_seq_scatter(attn_out)
+        if isinstance(k_cache, ops.Fp8KVCache):
+            # prefill into an FP8 cache: one quantizing store; the
+            # attention below still sees the fresh bf16 K/V
+            ops.fp8_kv_store(k, v, k_cache, v_cache, cu_seqlens, positions)
+        elif k_cache is not None:
+            # prefill: write all tokens into the cache
+            seq_id = torch.bucketize(
+                torch.arange(k.shape[0], device=k.device),
+                cu_seqlens[1:].long(), right=True)
+            k_cache[seq_id, positions] = k.detach().to(k_cache.dtype)
+            v_cache[seq_id, positions] = v.detach().to(v_cache.dtype)
+        return ops.attn_varlen(
+            q, k, v, cu_seqlens, max_seqlen, causal=True,
+            softmax_scale=scale, window=cfg.sliding_window,
+        )
 
-        if decode:
-            # one new token per sequence; write into cache then attend
-            bs = k_cache.shape[0]
-            assert q.shape[0] == bs
-            if fp8_kv:
-                ops.fp8_kv_append_ref(k, v, k_cache, v_cache, cache_seqlens)
-            else:
-                idx = (cache_seqlens.long() - 1).clamp(min=0)
-                b_idx = torch.arange(bs, device=x.device)
-                k_cache[b_idx, idx] = k.to(k_cache.dtype)
-                v_cache[b_idx, idx] = v.to(v_cache.dtype)
-            attn_out = ops.attn_decode(
-                q, k_cache, v_cache, cache_seqlens, scale,
-                window=cfg.sliding_window,
-            )
+    def _decode_attn(self, h, scale, positions, k_cache, v_cache,
+                     cache_seqlens):
+        """Eager decode, the route of every decode step the fused block does
+        not take: one new token per sequence, appended to the cache through
+        torch, then ops.attn_decode."""
+        cfg = self.cfg
+        q, k, v = self._qkv(h, fp8=self.fp8.get("qkv"))
+        if cfg.apply_rotary:
+            # graph-capture-safe length bound: never read positions back
+            q, k = self._rope(q, k, int(k_cache.shape[1]), positions)
+        bs = k_cache.shape[0]
+        assert q.shape[0] == bs
+        if isinstance(k_cache, ops.Fp8KVCache):
+            ops.fp8_kv_append_ref(k, v, k_cache, v_cache, cache_seqlens)
         else:
-            from realhf_amd.parallel import cp as cp_mod
+            idx = (cache_seqlens.long() - 1).clamp(min=0)
+            b_idx = torch.arange(bs, device=q.device)
+            k_cache[b_idx, idx] = k.to(k_cache.dtype)
+            v_cache[b_idx, idx] = v.to(v_cache.dtype)
+        return ops.attn_decode(q, k_cache, v_cache, cache_seqlens, scale,
+                               window=cfg.sliding_window)
 
-            cpctx = cp_mod.current()
-            if cpctx is not None:
-                # Ulysses context parallelism: tokens are sharded over
-                # the CP group; one all-to-all gives this rank ALL
-                # tokens for 1/cp of the heads, the varlen kernel runs
-                # on full sequences, and a second all-to-all restores
-                # the (token-shard, all-heads) layout (parallel/cp.py).
-                assert k_cache is None, "CP: no KV-cache prefill/generation"
-                assert q.shape[1] % cpctx.size == 0, (
-                    f"q heads {q.shape[1]} not divisible by cp {cpctx.size}")
-                assert k.shape[1] % cpctx.size == 0, (
-                    f"kv heads {k.shape[1]} not divisible by cp {cpctx.size}")
-                q = cp_mod.seq_gather_head_scatter(q)
-                k = cp_mod.seq_gather_head_scatter(k)
-                v = cp_mod.seq_gather_head_scatter(v)
-                attn_out = ops.attn_varlen(
-                    q, k, v, cpctx.info.full_cu, cpctx.info.full_max,
-                    causal=True, softmax_scale=scale,
-                    window=cfg.sliding_window,
-                )
-                attn_out = cp_mod.head_gather_seq_scatter(attn_out)
-            else:
-                if fp8_kv:
-                    # prefill into an FP8 cache: one quantizing store; the
-                    # attention below still sees the fresh bf16 K/V
-                    ops.fp8_kv_store(k, v, k_cache, v_cache, cu_seqlens,
-                                     positions)
-                elif k_cache is not None:
-                    # prefill: write all tokens into the cache
-                    bs = k_cache.shape[0]
-                    seq_id = torch.bucketize(
-                        torch.arange(x.shape[0], device=x.device),
-                        cu_seqlens[1:].long(),
-                        right=True,
-                    )
-                    k_cache[seq_id, positions] = k.detach().to(k_cache.dtype)
-                    v_cache[seq_id, positions] = v.detach().to(v_cache.dtype)
-                attn_out = ops.attn_varlen(
-                    q, k, v, cu_seqlens, max_seqlen, causal=True,
-                    softmax_scale=scale, window=cfg.sliding_window,
-                )
+    def _attn_epilogue(self, x, attn_out, sp, fp8):
+        """wo (+ LoRA delta), SP/TP reduce, bias, residual, MLP: the tail of
+        the two non-fused routes."""
+        i = self.i
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
+        wo = self.p[f"{i}.attn.wo.weight"]
         if "wo" in fp8:
-            o = ops.maybe_skinny_linear(attn_out, self.p[f"{i}.attn.wo.weight"],
-                                        fp8=fp8["wo"])
+            o = ops.maybe_skinny_linear(attn_out, wo, fp8=fp8["wo"])
         else:
-            o = _linear(attn_out, self.p[f"{i}.attn.wo.weight"])
+            o = _linear(attn_out, wo)
         if "wo" in self.lora:
             o = o + self._lora_delta(attn_out, "wo")
-        if sp:
-            o = mappings.reduce_scatter_to_sp_region(o)
-        else:
-            o = mappings.reduce_from_tp_region(o)
+        o = (mappings.reduce_scatter_to_sp_region(o) if sp
+             else mappings.reduce_from_tp_region(o))
         if f"{i}.attn.wo.bias" in self.p:
             o = o + self.p[f"{i}.attn.wo.bias"]
-        x = x + o
-        return self._mlp(x, sp, fp8=fp8)
+        return self._mlp(x + o, sp, fp8=fp8)
+
+    def _rope_append(self, C, qkv_raw, bias, k_cache, v_cache, cache_seqlens):
+        """The fused decode epilogue, one kernel for qkv-split + bias + RoPE
+        + KV append: returns q [bs, nq, hd] and writes the new K/V rows at
+        cache_seqlens - 1.  qkv_raw is bf16 or split-K slabs."""
+        cos, sin = self._rope_tables(int(k_cache.shape[1]), qkv_raw.device)
+        tail = (cache_seqlens, cos, sin, self.nq, self.cfg.apply_rotary)
+        if not isinstance(k_cache, ops.Fp8KVCache):
+            return C.rope_qkv_decode(qkv_raw, bias, k_cache, v_cache, *tail)
+        if ops.fp8_kv_enabled():
+            # the same epilogue, quantizing the K and V head rows
+            return C.rope_qkv_decode_fp8(
+                qkv_raw, bias, k_cache.codes, k_cache.scale,
+                v_cache.codes, v_cache.scale, *tail)
+        # REALHF_AMD_NO_FP8_KV=1, the A/B baseline and test oracle: the
+        # unchanged bf16 epilogue writes into scratch caches and the rows it
+        # wrote go through the reference quantizer, so the fp8 cache
+        # receives the rows the kernel above would have quantized;
+        # ops.attn_decode then takes the reference
+        ks, vs = (torch.empty(k_cache.shape, dtype=torch.bfloat16,
+                              device=qkv_raw.device) for _ in range(2))
+        q = C.rope_qkv_decode(qkv_raw, bias, ks, vs, *tail)
+        idx = (cache_seqlens.long() - 1).clamp(min=0)
+        b_idx = torch.arange(ks.shape[0], device=ks.device)
+        ops.fp8_kv_append_ref(ks[b_idx, idx], vs[b_idx, idx],
+                              k_cache, v_cache, cache_seqlens)
+        return q
+
+    def _fused_decode(self, x, h, sp, scale, k_cache, v_cache, cache_seqlens):
+        """The whole block for one decode step on HIP kernels that hand
+        split-K slabs across launch boundaries: QKV slabs are summed in the
+        rope/append epilogue's prologue, wo's in the fused (x + o) + mlp-norm,
+        gate/up's in the activation, and the down projection folds the
+        residual into its combine (_mlp_body)."""
+        i = self.i
+        cfg = self.cfg
+        fp8 = self.fp8
+        C = require_hip()
+        qkv_dim = (self.nq + 2 * self.nkv) * self.hd
+        merged = _maybe_merged(self.p, self._qkv_names, qkv_dim)
+        if merged is not None:
+            qkv_raw, _ = _decode_linear(h, merged, fp8.get("qkv"), slabs=True)
+        else:
+            qkv_raw = torch.cat(
+                [_linear(h, self.p[n]) for n in self._qkv_names], dim=-1)
+        bias = None
+        if f"{i}.attn.wq.bias" in self.p:
+            bias = torch.cat([self.p[f"{i}.attn.w{c}.bias"] for c in "qkv"],
+                             dim=0).to(qkv_raw.dtype)
+        q = self._rope_append(C, qkv_raw, bias, k_cache, v_cache,
+                              cache_seqlens)
+        attn_out = ops.attn_decode(q, k_cache, v_cache, cache_seqlens,
+                                   scale, window=cfg.sliding_window)
+        attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
+        # fused (x + o) + mlp-norm: plain RMS, or gemma's 1 + w mode
+        add_norm = None
+        if self.moe is None and cfg.norm_type == "rms":
+            add_norm = C.add_rmsnorm_fwd
+        elif (self.moe is None and cfg.norm_type == "gemma_rms"
+              and ops.gemma_ops_enabled()):
+            add_norm = C.gemma_add_rmsnorm_fwd
+        wo_bias = self.p.get(f"{i}.attn.wo.bias")
+        o, kind = _decode_linear(
+            attn_out, self.p[f"{i}.attn.wo.weight"], fp8.get("wo"),
+            slabs=(self.tp_size == 1 and wo_bias is None
+                   and add_norm is not None))
+        if kind != "slabs":
+            o = mappings.reduce_from_tp_region(o)
+            if wo_bias is not None:
+                o = o + wo_bias
+        if add_norm is None:
+            return self._mlp(x + o, sp, fp8=fp8)
+        h2, x2 = add_norm(o, x, self.p[f"{i}.mlp.ln.weight"],
+                          cfg.layer_norm_epsilon)
+        return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
 
     def _mlp(self, x, sp, fp8=None):
-        cfg = self.cfg
         i = self.i
-        h = _norm(cfg, x, self.p[f"{i}.mlp.ln.weight"], self.p.get(f"{i}.mlp.ln.bias"))
+        h = _norm(self.cfg, x, self.p[f"{i}.mlp.ln.weight"], self.p.get(f"{i}.mlp.ln.bias"))
         if self.moe is not None:
             return x + self.moe(h)
         return x + self._mlp_body(h, sp, fp8=fp8)  # residual not folded here
 
     def _mlp_body(self, h, sp, residual=None, fp8=None):
-        """norm-output -> MLP delta; with `residual` (tp==1 decode path)
-        the down-projection's combine kernel adds it in and the return
-        value is the full residual-stream output.  fp8: the decode step's
-        (q, scale) pairs for "gu" and "down" (FP8 weight-only decode)."""
+        """norm-output -> MLP delta; with `residual` (the fused decode block)
+        the return value is the full residual-stream output, the residual
+        added by the down projection's combine kernel where tp == 1 and
+        that kernel applies.  fp8: the decode step's (q, scale) pairs for
+        "gu" and "down" (FP8 weight-only decode)."""
         cfg = self.cfg
         i = self.i
         fp8 = fp8 or {}
-        fused_col = self.tp_size > 1 and torch.is_grad_enabled()
-        if fused_col and cfg.activation in ("silu", "geglu"):
-            idim_local = self.p[f"{i}.mlp.gate.weight"].shape[0]
-            merged_f = _maybe_merged(self.p, self._gu_names, 2 * idim_local)
-            if merged_f is None:
-                fused_col = False
-        elif fused_col:
-            fused_col = False  # single-up MLP: keep the mapping route
-        if not fused_col:
-            if sp:
-                h = mappings.gather_from_sp_region(h)
-            else:
-                h = mappings.copy_to_tp_region(h)
-        if cfg.activation in ("silu", "geglu"):
+        gated = cfg.activation in ("silu", "geglu")
+        merged = None
+        if gated:
             idim_local = self.p[f"{i}.mlp.gate.weight"].shape[0]
             merged = _maybe_merged(self.p, self._gu_names, 2 * idim_local)
-            act = None
+        # fused column linear (async bwd comm) over the merged gate/up; a
+        # single-up MLP keeps the mapping route
+        fused_col = (self.tp_size > 1 and torch.is_grad_enabled()
+                     and merged is not None)
+        if not fused_col:
+            h = (mappings.gather_from_sp_region(h) if sp
+                 else mappings.copy_to_tp_region(h))
+        if gated:
+            silu = cfg.activation == "silu"  # else geglu (gemma)
+            kind = "plain"
             if fused_col:
                 gu = mappings.column_parallel_linear(h, merged, sp)
             elif merged is not None:
-                if self.tp_size == 1 and (
-                    cfg.activation == "silu" or ops.gemma_ops_enabled()
-                ):
-                    # launch-boundary reduce: slabs summed in swiglu/geglu
-                    gu_parts = ops.skinny_linear_nc(h, merged,
-                                                    fp8=fp8.get("gu"))
-                    if gu_parts is not None:
-                        from realhf_amd import ops as _ops_pkg
-
-                        C = _ops_pkg.require_hip()
-                        act = (C.swiglu_fwd if cfg.activation == "silu"
-                               else C.geglu_fwd)(gu_parts)
-                if act is None:
-                    gu = ops.maybe_skinny_linear(h, merged, fp8=fp8.get("gu"))
-                    if gu is None:
-                        gu = _linear(h, merged)
-            elif not fused_col:
+                # launch-boundary reduce: slabs summed in swiglu/geglu
+                gu, kind = _decode_linear(
+                    h, merged, fp8.get("gu"),
+                    slabs=(self.tp_size == 1
+                           and (silu or ops.gemma_ops_enabled())))
+            else:
                 gu = torch.cat(
-                    [_linear(h, self.p[n]) for n in self._gu_names], dim=-1
-                )
-            if act is not None:
-                pass
-            elif cfg.activation == "silu":
-                act = ops.swiglu(gu)
-            else:  # geglu (gemma)
-                act = ops.geglu(gu)
+                    [_linear(h, self.p[n]) for n in self._gu_names], dim=-1)
+            if kind == "slabs":
+                C = require_hip()
+                act = (C.swiglu_fwd if silu else C.geglu_fwd)(gu)
+            else:
+                act = ops.swiglu(gu) if silu else ops.geglu(gu)
         else:
             up = _linear(h, self.p[f"{i}.mlp.up.weight"], self.p.get(f"{i}.mlp.up.bias"))
             act = F.gelu(up, approximate="tanh")
-        wd = self.p[f"{i}.mlp.down.weight"]
-        use_resid_fold = residual is not None and self.tp_size == 1
-        down = ops.maybe_skinny_linear(
-            act, wd, residual=residual if use_resid_fold else None,
-            fp8=fp8.get("down"),
-        )
-        folded = down is not None and use_resid_fold
-        if down is None:
-            down = _linear(act, wd)
-        if folded:
+        down, kind = _decode_linear(
+            act, self.p[f"{i}.mlp.down.weight"], fp8.get("down"),
+            residual=residual if self.tp_size == 1 else None)
+        if kind == "folded":
             return down  # residual already added
-        if residual is not None:
-            # fold failed (shape/grad): plain add at the end
-            pass
-        if sp:
-            down = mappings.reduce_scatter_to_sp_region(down)
-        else:
-            down = mappings.reduce_from_tp_region(down)
+        down = (mappings.reduce_scatter_to_sp_region(down) if sp
+                else mappings.reduce_from_tp_region(down))
         if f"{i}.mlp.down.bias" in self.p:
             down = down + self.p[f"{i}.mlp.down.bias"]
         if residual is not None:

@@ -168,12 +168,17 @@ static SgShape sg_shape(const torch::Tensor& x, const torch::Tensor& w,
   return s;
 }
 
+// the [nks, M, N] slab view of the workspace
+static torch::Tensor sg_slabs(const torch::Tensor& out32_ws, const SgShape& s) {
+  return out32_ws.narrow(0, 0, (long)s.nks * s.M * s.N)
+      .view({(long)s.nks, (long)s.M, (long)s.N});
+}
+
 // launch the split-K partial kernel; returns the [nks, M, N] slab view
 static torch::Tensor sg_partials(const torch::Tensor& x, const torch::Tensor& w,
                                  const torch::Tensor& out32_ws,
                                  const SgShape& s) {
-  auto out32 = out32_ws.narrow(0, 0, (long)s.nks * s.M * s.N)
-                   .view({(long)s.nks, (long)s.M, (long)s.N});
+  auto out32 = sg_slabs(out32_ws, s);
   auto launch = [&](auto nb, auto wvs) {
     dim3 grid(s.N / (16 * wvs.value), s.nks);
     hipLaunchKernelGGL((skinny_gemm_kernel<nb.value, wvs.value>), grid,
@@ -195,6 +200,22 @@ static const bf16* sg_resid_ptr(const c10::optional<torch::Tensor>& residual,
   if (!residual.has_value()) return nullptr;
   TORCH_CHECK(residual->is_contiguous() && residual->numel() == n);
   return (const bf16*)residual->data_ptr();
+}
+
+// launch the combine kernel over the slabs (residual, optional [M, N] bf16,
+// is folded into it); returns the bf16 [M, N] result, allocated like x
+static torch::Tensor sg_combine(const torch::Tensor& out32,
+                                const torch::Tensor& x, const SgShape& s,
+                                const c10::optional<torch::Tensor>& residual) {
+  auto out = torch::empty({s.M, (long)s.N}, x.options());
+  long n = (long)s.M * s.N;
+  int cgrid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
+  const bf16* rptr = sg_resid_ptr(residual, n);
+  hipLaunchKernelGGL(sg_combine_kernel, dim3(cgrid), dim3(256), 0,
+    cur_stream(), out32.data_ptr<float>(), rptr, (bf16*)out.data_ptr(), n,
+    s.nks);
+  CHECK_CUDA_OK();
+  return out;
 }
 
 torch::Tensor skinny_gemm_nc(torch::Tensor x, torch::Tensor w,
@@ -341,22 +362,12 @@ torch::Tensor skinny_gemm2(torch::Tensor x, torch::Tensor w,
   return out;
 }
 
-// partials, then the combine kernel (residual, optional [M, N] bf16, is
-// folded into it)
+// partials, then the combine kernel
 torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
                           torch::Tensor out32_ws, long splitk,
                           c10::optional<torch::Tensor> residual) {
   const SgShape s = sg_shape(x, w, out32_ws, splitk);
-  auto out32 = sg_partials(x, w, out32_ws, s);
-  auto out = torch::empty({s.M, (long)s.N}, x.options());
-  long n = (long)s.M * s.N;
-  int cgrid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
-  const bf16* rptr = sg_resid_ptr(residual, n);
-  hipLaunchKernelGGL(sg_combine_kernel, dim3(cgrid), dim3(256), 0,
-    cur_stream(), out32.data_ptr<float>(), rptr, (bf16*)out.data_ptr(), n,
-    s.nks);
-  CHECK_CUDA_OK();
-  return out;
+  return sg_combine(sg_partials(x, w, out32_ws, s), x, s, residual);
 }
 
 // ---------------------------------------------------------------------------
@@ -485,8 +496,7 @@ static torch::Tensor sg_partials_fp8(const torch::Tensor& x,
                                      const torch::Tensor& scale,
                                      const torch::Tensor& out32_ws,
                                      const SgShape& s) {
-  auto out32 = out32_ws.narrow(0, 0, (long)s.nks * s.M * s.N)
-                   .view({(long)s.nks, (long)s.M, (long)s.N});
+  auto out32 = sg_slabs(out32_ws, s);
   hipLaunchKernelGGL((skinny_gemm_fp8_kernel<4>), dim3(s.N / SG_TN, s.nks),
     dim3(256), s.lds, cur_stream(), (const bf16*)x.data_ptr(),
     (const unsigned char*)q.data_ptr(), scale.data_ptr<float>(),
@@ -508,14 +518,5 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor x, torch::Tensor q,
                               long splitk,
                               c10::optional<torch::Tensor> residual) {
   const SgShape s = sg_shape_fp8(x, q, scale, out32_ws, splitk);
-  auto out32 = sg_partials_fp8(x, q, scale, out32_ws, s);
-  auto out = torch::empty({s.M, (long)s.N}, x.options());
-  long n = (long)s.M * s.N;
-  int cgrid = (int)std::min<long>((n / 4 + 255) / 256, 2048);
-  const bf16* rptr = sg_resid_ptr(residual, n);
-  hipLaunchKernelGGL(sg_combine_kernel, dim3(cgrid), dim3(256), 0,
-    cur_stream(), out32.data_ptr<float>(), rptr, (bf16*)out.data_ptr(), n,
-    s.nks);
-  CHECK_CUDA_OK();
-  return out;
+  return sg_combine(sg_partials_fp8(x, q, scale, out32_ws, s), x, s, residual);
 }

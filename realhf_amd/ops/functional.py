@@ -43,9 +43,17 @@ from realhf_amd import ops as _ops
 
 # Head dims the HIP attention kernels (attn_varlen fwd/bwd, attn_decode) are
 # instantiated for.  The one gate for every caller: the varlen/decode
-# dispatch below, the fused decode epilogue (models/layers.py) and hipGraph
-# decode (models/generation.py, parallel/pp.py).
+# dispatch and the FP8 KV store below, the fused decode block's
+# fused_decode_blocker (models/layers.py) and hipGraph decode
+# (decode_graph_supported in models/generation.py, parallel/pp.py).
 HIP_ATTN_HEAD_DIMS = (64, 128, 256)
+
+
+def hip_attn_supported(dtype, head_dim: int, device) -> bool:
+    """Do the HIP attention kernels take this dtype and head dim on this
+    device?  bf16 on a GPU at one of HIP_ATTN_HEAD_DIMS."""
+    return (torch.device(device).type == "cuda" and dtype == torch.bfloat16
+            and head_dim in HIP_ATTN_HEAD_DIMS)
 
 
 # ---------------------------------------------------------------------------
@@ -429,8 +437,7 @@ def attn_varlen(q, k, v, cu_seqlens, max_seqlen, causal=True, softmax_scale=None
         window = None  # window wider than any sequence: plain causal
     if (
         _ops.use_hip(q)
-        and q.dtype == torch.bfloat16
-        and q.shape[-1] in HIP_ATTN_HEAD_DIMS
+        and hip_attn_supported(q.dtype, q.shape[-1], q.device)
         and (window is None or causal)
     ):
         return _AttnVarlenFn.apply(
@@ -481,26 +488,20 @@ def attn_decode(q, k_cache, v_cache, cache_seqlens, softmax_scale=None,
     scale = softmax_scale or (1.0 / math.sqrt(q.shape[-1]))
     if window is not None and k_cache.shape[1] <= window:
         window = None  # cache can never exceed the window: plain causal
+    hip = (
+        _ops.use_hip(q)
+        and hip_attn_supported(q.dtype, q.shape[-1], q.device)
+        and q.shape[1] // k_cache.shape[2] in (1, 2, 4, 8)
+    )
     if isinstance(k_cache, Fp8KVCache):
-        if (
-            _ops.use_hip(q)
-            and fp8_kv_enabled()
-            and q.dtype == torch.bfloat16
-            and q.shape[-1] in HIP_ATTN_HEAD_DIMS
-            and q.shape[1] // k_cache.shape[2] in (1, 2, 4, 8)
-        ):
+        if hip and fp8_kv_enabled():
             C = _ops.require_hip()
             return C.attn_decode_fp8(q, k_cache.codes, k_cache.scale,
                                      v_cache.codes, v_cache.scale,
                                      cache_seqlens, scale, int(window or 0))
         return attn_decode_fp8_ref(q, k_cache, v_cache, cache_seqlens, scale,
                                    window=window)
-    if (
-        _ops.use_hip(q)
-        and q.dtype == torch.bfloat16
-        and q.shape[-1] in HIP_ATTN_HEAD_DIMS
-        and q.shape[1] // k_cache.shape[2] in (1, 2, 4, 8)
-    ):
+    if hip:
         C = _ops.require_hip()
         return C.attn_decode(q, k_cache, v_cache, cache_seqlens, scale,
                              int(window or 0))
@@ -716,17 +717,32 @@ def merge_intervals(intervals: List[Tuple[int, int]]) -> List[Tuple[int, int]]:
 # projections (o/down: ~1.6-2x over hipBLASLt), loses on very wide N —
 # callers pick per shape (tools/bench_skinny.py is the A/B harness).
 # ---------------------------------------------------------------------------
-def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
-                        residual: Optional[torch.Tensor] = None,
-                        fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                        ) -> Optional[torch.Tensor]:
-    """fp8 = (q, scale) from quantize_rows_e4m3(w): stream the e4m3 codes
-    instead of w (skinny_gemm_fp8) under the same eligibility rules plus
-    K % 64 == 0.  With a pair the result is never None: whatever the kernel
-    does not take (CPU, M > 16, REALHF_AMD_NO_FP8_SKINNY=1) goes through
-    fp8_linear_ref, so the weights in use are the quantized ones either way."""
-    if fp8 is not None:
-        w = fp8[0]
+def _sg_kslice_max() -> int:
+    """Max K elements per split-K slice (tunes workgroup count); A/B via
+    REALHF_AMD_SG_KSLICE, default 1024."""
+    global _SG_KSLICE
+    if _SG_KSLICE is None:
+        _SG_KSLICE = int(os.environ.get("REALHF_AMD_SG_KSLICE", 1024))
+    return _SG_KSLICE
+
+
+_SG_KSLICE = None
+
+
+def skinny_splitk(K: int) -> int:
+    """The split-K factor of the skinny GEMMs: 8, doubled while a K slice
+    would be longer than _sg_kslice_max()."""
+    splitk = 8
+    while K // splitk > _sg_kslice_max():
+        splitk *= 2
+    return splitk
+
+
+def _skinny_plan(x: torch.Tensor, w: torch.Tensor, fp8):
+    """What maybe_skinny_linear and skinny_linear_nc share: None where the
+    skinny kernels do not take x @ w^T (w: the e4m3 codes when there is an
+    fp8 pair, which also asks for K % 64 == 0), else (extension, split-K
+    factor, shared fp32 workspace)."""
     if not (
         x.is_cuda
         and x.dtype == torch.bfloat16
@@ -739,29 +755,41 @@ def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
         and w.shape[0] % 64 == 0
         and w.shape[1] % (32 if fp8 is None else 64) == 0
         and (fp8 is None or fp8_skinny_enabled())
-        # in-context the weight-streaming kernel also edges out hipBLASLt
-        # on the wide-N shapes (A/B: 3.09 vs 3.05 samples/s); opt out with
-        # REALHF_AMD_NO_SKINNY_WIDE=1
-        and (
-            w.shape[0] <= 2 * w.shape[1]
-            or os.environ.get("REALHF_AMD_NO_SKINNY_WIDE") != "1"
-        )
         and _ops.hip_available()
     ):
-        if fp8 is not None:
-            return fp8_linear_ref(x, fp8[0], fp8[1], residual)
         return None
     from realhf_amd.base.constants import get_global_memory_buffer
 
-    C = _ops.require_hip()
-    M, K = x.shape
-    N = w.shape[0]
-    splitk = 8
-    while K // splitk > _sg_kslice_max():
-        splitk *= 2
+    splitk = skinny_splitk(x.shape[1])
     ws = get_global_memory_buffer().get_tensor(
-        (2 * splitk * 16 * N,), torch.float32, "skinny_gemm_ws"
+        (2 * splitk * 16 * w.shape[0],), torch.float32, "skinny_gemm_ws"
     )
+    return _ops.require_hip(), splitk, ws
+
+
+def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
+                        residual: Optional[torch.Tensor] = None,
+                        fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                        ) -> Optional[torch.Tensor]:
+    """x @ w^T (+ residual, folded into the combine) on the skinny kernel,
+    None where _skinny_plan does not take it.  fp8 = (q, scale) from
+    quantize_rows_e4m3(w): stream the e4m3 codes instead of w
+    (skinny_gemm_fp8).  With a pair the result is never None: whatever the
+    kernel does not take (CPU, M > 16, REALHF_AMD_NO_FP8_SKINNY=1) goes through
+    fp8_linear_ref, so the weights in use are the quantized ones either way."""
+    if fp8 is not None:
+        w = fp8[0]
+    # in-context the weight-streaming kernel also edges out hipBLASLt on the
+    # wide-N shapes (A/B: 3.09 vs 3.05 samples/s); opt out with
+    # REALHF_AMD_NO_SKINNY_WIDE=1
+    wide_ok = (w.shape[0] <= 2 * w.shape[1]
+               or os.environ.get("REALHF_AMD_NO_SKINNY_WIDE") != "1")
+    plan = _skinny_plan(x, w, fp8) if wide_ok else None
+    if plan is None:
+        if fp8 is not None:
+            return fp8_linear_ref(x, fp8[0], fp8[1], residual)
+        return None
+    C, splitk, ws = plan
     if residual is not None:
         residual = residual.contiguous()
     if fp8 is not None:
@@ -775,18 +803,6 @@ def maybe_skinny_linear(x: torch.Tensor, w: torch.Tensor,
     return C.skinny_gemm(x, w, ws, splitk, residual)
 
 
-def _sg_kslice_max() -> int:
-    """Max K elements per split-K slice (tunes workgroup count); A/B via
-    REALHF_AMD_SG_KSLICE, default 1024."""
-    global _SG_KSLICE
-    if _SG_KSLICE is None:
-        _SG_KSLICE = int(os.environ.get("REALHF_AMD_SG_KSLICE", 1024))
-    return _SG_KSLICE
-
-
-_SG_KSLICE = None
-
-
 def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor,
                      fp8: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                      ) -> Optional[torch.Tensor]:
@@ -796,36 +812,14 @@ def skinny_linear_nc(x: torch.Tensor, w: torch.Tensor,
     add_rmsnorm_fwd / swiglu_fwd all accept slabs).  The slabs live in the
     shared skinny workspace — consume them before the next skinny call.
     fp8 = (q, scale): the slabs come from skinny_gemm_fp8_nc, row scale
-    already applied; None where that kernel does not apply (the caller then
-    goes on to maybe_skinny_linear with the same pair)."""
+    already applied; None where _skinny_plan does not take it (the caller
+    then goes on to maybe_skinny_linear with the same pair)."""
     if fp8 is not None:
         w = fp8[0]
-    if not (
-        x.is_cuda
-        and x.dtype == torch.bfloat16
-        and not torch.is_grad_enabled()
-        and x.dim() == 2
-        and x.shape[0] <= 16
-        and x.stride(1) == 1
-        and x.stride(0) == x.shape[1]
-        and w.stride(1) == 1
-        and w.shape[0] % 64 == 0
-        and w.shape[1] % (32 if fp8 is None else 64) == 0
-        and (fp8 is None or fp8_skinny_enabled())
-        and _ops.hip_available()
-    ):
+    plan = _skinny_plan(x, w, fp8)
+    if plan is None:
         return None
-    from realhf_amd.base.constants import get_global_memory_buffer
-
-    C = _ops.require_hip()
-    K = x.shape[1]
-    N = w.shape[0]
-    splitk = 8
-    while K // splitk > _sg_kslice_max():
-        splitk *= 2
-    ws = get_global_memory_buffer().get_tensor(
-        (2 * splitk * 16 * N,), torch.float32, "skinny_gemm_ws"
-    )
+    C, splitk, ws = plan
     if fp8 is not None:
         return C.skinny_gemm_fp8_nc(x, fp8[0], fp8[1], ws, splitk)
     return C.skinny_gemm_nc(x, w, ws, splitk)
@@ -995,8 +989,7 @@ def fp8_kv_store(k, v, k_cache: Fp8KVCache, v_cache: Fp8KVCache, cu_seqlens,
     if (
         _ops.use_hip(k)
         and fp8_kv_enabled()
-        and k.dtype == torch.bfloat16
-        and k.shape[-1] in HIP_ATTN_HEAD_DIMS
+        and hip_attn_supported(k.dtype, k.shape[-1], k.device)
     ):
         C = _ops.require_hip()
 

@@ -50,13 +50,6 @@ def stats(ts):
     return min(ts), statistics.median(ts), max(ts)
 
 
-def splitk_for(K):  # what maybe_skinny_linear / skinny_linear_nc choose
-    sk = 8
-    while K // sk > 1024:
-        sk *= 2
-    return sk
-
-
 def bench_shapes(a):
     M = 16
     ws = torch.empty(2 * 16 * 16 * 22016, dtype=torch.float32, device="cuda")
@@ -66,7 +59,7 @@ def bench_shapes(a):
           f"{'bf16 us min/med/max':>24} {'fp8 us min/med/max':>24} "
           f"{'bf16 TB/s':>9} {'fp8 TB/s':>9} {'bf16/fp8':>8}")
     for name, N, K in SHAPES:
-        sk = splitk_for(K)
+        sk = F.skinny_splitk(K)  # what the model path chooses
         # the same number of copies in both arms; the fp8 arm alone spans
         # --rotate-gb, the bf16 arm twice that
         n = max(2, int(a.rotate_gb * 1e9 / (N * K)) + 1)
