@@ -2,6 +2,7 @@
 // All bf16/f16 I/O is 8-element vectorized (guide G13); trig tables are
 // host-precomputed (guide Appendix B: no sinf/cosf on device).
 #include "common.h"
+#include "slab_sum.h"
 
 // ---------------------------------------------------------------------------
 // RoPE: x [total, nh, hd], cos/sin [maxlen, hd/2] fp32, positions [total].
@@ -117,8 +118,9 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ out,
 // slab variant: gate_up comes in as fp32 split-K partial slabs
 // [nks, tokens, 2I] from skinny_gemm_nc (launch-boundary reduce)
 template <typename T, bool GELU = false>
-__global__ void swiglu_slab_kernel(const float* __restrict__ parts, int nks,
-                                   T* __restrict__ out, long tokens, int I) {
+__global__ __launch_bounds__(256) void swiglu_slab_kernel(
+    const float* __restrict__ parts, int nks, T* __restrict__ out, long tokens,
+    int I) {
   const long sstride = tokens * (2L * I);
   long n = tokens * (I / 8);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -127,26 +129,16 @@ __global__ void swiglu_slab_kernel(const float* __restrict__ parts, int nks,
     int d0 = (int)(i % (I / 8)) * 8;
     const float* g = parts + t * (2L * I) + d0;
     const float* u = g + I;
-    float gf[8], uf[8];
-    #pragma unroll
-    for (int j = 0; j < 8; j += 4) {
-      *(float4v*)(gf + j) = *(const float4v*)(g + j);
-      *(float4v*)(uf + j) = *(const float4v*)(u + j);
-    }
-    for (int s = 1; s < nks; s++) {
-      #pragma unroll
-      for (int j = 0; j < 8; j += 4) {
-        float4v pg = *(const float4v*)(g + (long)s * sstride + j);
-        float4v pu = *(const float4v*)(u + (long)s * sstride + j);
-        #pragma unroll
-        for (int q = 0; q < 4; q++) { gf[j + q] += pg[q]; uf[j + q] += pu[q]; }
-      }
-    }
+    // gate 0..3, gate 4..7, up 0..3, up 4..7
+    const float* const p[4] = {g, g + 4, u, u + 4};
+    float4v acc[4];
+    slab_sum<4>(acc, p, sstride, nks);
     short o[8];
     #pragma unroll
     for (int j = 0; j < 8; j++) {
-      float sg = gf[j] / (1.f + __expf(-glu_sig_arg<GELU>(gf[j])));
-      ((T*)o)[j] = from_f32<T>(sg * uf[j]);
+      const float gf = acc[j / 4][j % 4], uf = acc[2 + j / 4][j % 4];
+      float sg = gf / (1.f + __expf(-glu_sig_arg<GELU>(gf)));
+      ((T*)o)[j] = from_f32<T>(sg * uf);
     }
     *(short8*)(out + t * (long)I + d0) = *(short8*)o;
   }

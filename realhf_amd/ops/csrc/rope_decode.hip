@@ -19,9 +19,10 @@
 // threads, hd/8 is 8, 16 or 32, and nwork is a multiple of it.
 #include "common.h"
 #include "fp8_e4m3.h"
+#include "slab_sum.h"
 
 template <bool SLAB, int FP8_HD = 0>
-__global__ void rope_qkv_decode_kernel(
+__global__ __launch_bounds__(256) void rope_qkv_decode_kernel(
     const void* __restrict__ qkv_in,  // bf16 [bs, qkvd] | fp32 [nks, bs, qkvd]
     const bf16* __restrict__ bias,  // [(nq+2nkv)*hd] or null
     bf16* __restrict__ q_out,  // [bs, nq, hd]
@@ -44,19 +45,28 @@ __global__ void rope_qkv_decode_kernel(
     const int d0 = quad * 4;
     const int pos = max(cache_seqlens[b] - 1, 0);
 
+    // everything that does not depend on the slab sum goes out before it:
+    // bias and cos / sin (V heads load theirs too and ignore them) are in
+    // flight with the first slab batch
+    short4v b1 = {}, b2 = {};
+    float4v c = {}, s = {};
+    if (bias) {
+      b1 = *(const short4v*)((const short*)bias + (long)h * hd + d0);
+      b2 = *(const short4v*)((const short*)bias + (long)h * hd + hd2 + d0);
+    }
+    if (apply_rope) {
+      c = *(const float4v*)(cosb + (long)pos * hd2 + d0);
+      s = *(const float4v*)(sinb + (long)pos * hd2 + d0);
+    }
     float4v f1, f2;
     if constexpr (SLAB) {
       const float* src =
           (const float*)qkv_in + (long)b * qkv_stride + (long)h * hd;
-      const long sstride = (long)bs * qkv_stride;
-      f1 = *(const float4v*)(src + d0);
-      f2 = *(const float4v*)(src + hd2 + d0);
-      for (int s = 1; s < nks; s++) {
-        float4v p1 = *(const float4v*)(src + (long)s * sstride + d0);
-        float4v p2 = *(const float4v*)(src + (long)s * sstride + hd2 + d0);
-        #pragma unroll
-        for (int j = 0; j < 4; j++) { f1[j] += p1[j]; f2[j] += p2[j]; }
-      }
+      const float* const p[2] = {src + d0, src + hd2 + d0};
+      float4v acc[2];
+      slab_sum<2>(acc, p, (long)bs * qkv_stride, nks);
+      f1 = acc[0];
+      f2 = acc[1];
     } else {
       const bf16* src =
           (const bf16*)qkv_in + (long)b * qkv_stride + (long)h * hd;
@@ -69,8 +79,6 @@ __global__ void rope_qkv_decode_kernel(
       }
     }
     if (bias) {
-      short4v b1 = *(const short4v*)((const short*)bias + (long)h * hd + d0);
-      short4v b2 = *(const short4v*)((const short*)bias + (long)h * hd + hd2 + d0);
       #pragma unroll
       for (int j = 0; j < 4; j++) {
         f1[j] += __bfloat162float(((const bf16*)&b1)[j]);
@@ -90,8 +98,6 @@ __global__ void rope_qkv_decode_kernel(
     }
     short o1[4], o2[4];
     if (rope) {
-      float4v c = *(const float4v*)(cosb + (long)pos * hd2 + d0);
-      float4v s = *(const float4v*)(sinb + (long)pos * hd2 + d0);
       #pragma unroll
       for (int j = 0; j < 4; j++) {
         ((bf16*)o1)[j] = __float2bfloat16(f1[j] * c[j] - f2[j] * s[j]);
