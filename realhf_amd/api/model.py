@@ -87,6 +87,18 @@ class ReaLModelConfig:
     # mistral-style sliding-window attention: each token attends to the
     # previous `sliding_window` tokens (inclusive of itself); None = full
     sliding_window: Optional[int] = None
+    # which blocks use sliding_window, one bool per layer (HF layer_types ==
+    # "sliding_attention"); None = every layer (mistral)
+    sliding_window_layers: Optional[List[bool]] = None
+    # gemma-2: soft-cap cap * tanh(x / cap) on the attention logits and on the
+    # LM head's logits; softmax scale query_pre_attn_scalar ** -0.5 in place of
+    # head_dim ** -0.5; post_norms adds a norm on the attention output and one
+    # on the MLP output, each before its residual add ({i}.attn.post_ln,
+    # {i}.mlp.post_ln).  None / False = off
+    attn_logit_softcap: Optional[float] = None
+    final_logit_softcap: Optional[float] = None
+    query_pre_attn_scalar: Optional[float] = None
+    post_norms: bool = False
     # dropout (0 for RLHF)
     attn_pdrop: float = 0.0
     resid_pdrop: float = 0.0
@@ -103,6 +115,25 @@ class ReaLModelConfig:
         if self.n_kv_heads is None:
             self.n_kv_heads = self.n_heads
         assert self.n_heads % self.n_kv_heads == 0 or self.n_kv_heads % self.n_heads == 0
+        if self.sliding_window_layers is not None:
+            assert len(self.sliding_window_layers) == self.n_layers
+
+    def layer_window(self, layer_idx: int) -> Optional[int]:
+        """sliding_window of block layer_idx (1-based, as the blocks count),
+        None where that block attends to the full context."""
+        if self.sliding_window is None:
+            return None
+        sel = self.sliding_window_layers
+        if sel is not None and not sel[layer_idx - 1]:
+            return None
+        return self.sliding_window
+
+    @property
+    def softmax_scale(self) -> float:
+        """query_pre_attn_scalar ** -0.5 when set (gemma-2), else head_dim ** -0.5."""
+        import math
+
+        return 1.0 / math.sqrt(self.query_pre_attn_scalar or self.head_dim)
 
     @property
     def torch_dtype(self):
@@ -118,7 +149,7 @@ class ReaLModelConfig:
             mlp = 2 * h * i
         if self.moe is not None:
             mlp = mlp * self.moe.num_experts + h * self.moe.num_experts
-        per_layer = attn + mlp + 2 * h
+        per_layer = attn + mlp + (4 if self.post_norms else 2) * h
         emb = v * h
         head = h if self.is_critic else (0 if self.tied_embedding else v * h)
         return emb + self.n_layers * per_layer + head + h

@@ -21,7 +21,6 @@ decode block, which runs exactly when fused_decode_blocker() names no reason
 (generation's quant blockers are built on the same function).  Every decode
 projection goes down one ladder, _decode_linear().
 """
-import math
 import os
 from typing import Dict, Optional, Tuple
 
@@ -163,6 +162,10 @@ class ReaLModelBlock(nn.Module):
         self.nkv = max(cfg.n_kv_heads // tp_size, 1)
         assert cfg.n_kv_heads % tp_size == 0 or tp_size % cfg.n_kv_heads == 0
         self.hd = cfg.head_dim
+        # this block's sliding window (gemma-2 alternates; None = full) and
+        # attention logit soft-cap
+        self.window = cfg.layer_window(layer_idx)
+        self.softcap = cfg.attn_logit_softcap
         i = layer_idx
         self._qkv_names = [f"{i}.attn.wq.weight", f"{i}.attn.wk.weight", f"{i}.attn.wv.weight"]
         self._gu_names = (
@@ -277,7 +280,7 @@ class ReaLModelBlock(nn.Module):
             h = (mappings.gather_from_sp_region(h) if sp
                  else mappings.copy_to_tp_region(h))
 
-        scale = 1.0 / math.sqrt(self.hd)
+        scale = cfg.softmax_scale
         if cfg.scale_attn_by_inverse_layer_idx:
             scale = scale / float(self.i)
 
@@ -352,7 +355,8 @@ class ReaLModelBlock(nn.Module):
             v = cp_mod.seq_gather_head_scatter(v)
             attn_out = ops.attn_varlen(
                 q, k, v, cpctx.info.full_cu, cpctx.info.full_max,
-                causal=True, softmax_scale=scale, window=cfg.sliding_window)
+                causal=True, softmax_scale=scale, window=self.window,
+                softcap=self.softcap)
             return cp_mod.head_gather_seq_scatter(attn_out)
         if isinstance(k_cache, ops.Fp8KVCache):
             # prefill into an FP8 cache: one quantizing store; the
@@ -367,7 +371,7 @@ class ReaLModelBlock(nn.Module):
             v_cache[seq_id, positions] = v.detach().to(v_cache.dtype)
         return ops.attn_varlen(
             q, k, v, cu_seqlens, max_seqlen, causal=True,
-            softmax_scale=scale, window=cfg.sliding_window,
+            softmax_scale=scale, window=self.window, softcap=self.softcap,
         )
 
     def _decode_attn(self, h, scale, positions, k_cache, v_cache,
@@ -390,12 +394,13 @@ class ReaLModelBlock(nn.Module):
             k_cache[b_idx, idx] = k.to(k_cache.dtype)
             v_cache[b_idx, idx] = v.to(v_cache.dtype)
         return ops.attn_decode(q, k_cache, v_cache, cache_seqlens, scale,
-                               window=cfg.sliding_window)
+                               window=self.window, softcap=self.softcap)
 
     def _attn_epilogue(self, x, attn_out, sp, fp8):
-        """wo (+ LoRA delta), SP/TP reduce, bias, residual, MLP: the tail of
-        the two non-fused routes."""
+        """wo (+ LoRA delta), SP/TP reduce, bias, (post norm,) residual, MLP:
+        the tail of the two non-fused routes."""
         i = self.i
+        cfg = self.cfg
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
         wo = self.p[f"{i}.attn.wo.weight"]
         if "wo" in fp8:
@@ -408,6 +413,8 @@ class ReaLModelBlock(nn.Module):
              else mappings.reduce_from_tp_region(o))
         if f"{i}.attn.wo.bias" in self.p:
             o = o + self.p[f"{i}.attn.wo.bias"]
+        if cfg.post_norms:  # after the TP reduce: the norm needs whole rows
+            o = _norm(cfg, o, self.p[f"{i}.attn.post_ln.weight"], None)
         return self._mlp(x + o, sp, fp8=fp8)
 
     def _rope_append(self, C, qkv_raw, bias, k_cache, v_cache, cache_seqlens):
@@ -461,7 +468,8 @@ class ReaLModelBlock(nn.Module):
         q = self._rope_append(C, qkv_raw, bias, k_cache, v_cache,
                               cache_seqlens)
         attn_out = ops.attn_decode(q, k_cache, v_cache, cache_seqlens,
-                                   scale, window=cfg.sliding_window)
+                                   scale, window=self.window,
+                                   softcap=self.softcap)
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
         # fused (x + o) + mlp-norm: plain RMS, or gemma's 1 + w mode
         add_norm = None
@@ -474,23 +482,36 @@ class ReaLModelBlock(nn.Module):
         o, kind = _decode_linear(
             attn_out, self.p[f"{i}.attn.wo.weight"], fp8.get("wo"),
             slabs=(self.tp_size == 1 and wo_bias is None
-                   and add_norm is not None))
+                   and add_norm is not None and not cfg.post_norms))
         if kind != "slabs":
             o = mappings.reduce_from_tp_region(o)
             if wo_bias is not None:
                 o = o + wo_bias
+        if cfg.post_norms:
+            # gemma-2 sandwich norms: wo through the combine form (the post
+            # norm needs the summed rows), norm, then the usual fused
+            # (x + o) + mlp-norm
+            o = _norm(cfg, o, self.p[f"{i}.attn.post_ln.weight"], None)
         if add_norm is None:
             return self._mlp(x + o, sp, fp8=fp8)
         h2, x2 = add_norm(o, x, self.p[f"{i}.mlp.ln.weight"],
                           cfg.layer_norm_epsilon)
+        if cfg.post_norms:
+            # down without the residual fold: its output is normed first
+            d = self._mlp_body(h2, sp, fp8=fp8)
+            return x2 + _norm(cfg, d, self.p[f"{i}.mlp.post_ln.weight"], None)
         return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
 
     def _mlp(self, x, sp, fp8=None):
         i = self.i
         h = _norm(self.cfg, x, self.p[f"{i}.mlp.ln.weight"], self.p.get(f"{i}.mlp.ln.bias"))
         if self.moe is not None:
-            return x + self.moe(h)
-        return x + self._mlp_body(h, sp, fp8=fp8)  # residual not folded here
+            d = self.moe(h)
+        else:
+            d = self._mlp_body(h, sp, fp8=fp8)  # residual not folded here
+        if self.cfg.post_norms:
+            d = _norm(self.cfg, d, self.p[f"{i}.mlp.post_ln.weight"], None)
+        return x + d
 
     def _mlp_body(self, h, sp, residual=None, fp8=None):
         """norm-output -> MLP delta; with `residual` (the fused decode block)
@@ -572,12 +593,20 @@ class OutputHead(nn.Module):
         tp = constants.tp_world_size() if constants.has_current() else 1
         if tp > 1 and torch.is_grad_enabled():
             # fused copy-to-TP + GEMM: bwd all-reduce overlaps dW
-            return mappings.column_parallel_linear(h, w, False)
+            return self._cap(mappings.column_parallel_linear(h, w, False))
         h = mappings.copy_to_tp_region(h)
         if not torch.is_grad_enabled():
             # decode: the vocab head streams 262 MB of weights per token —
             # the weight-streaming skinny kernel beats hipBLASLt at M<=16
             o = ops.maybe_skinny_linear(h, w)
             if o is not None:
-                return o
-        return _linear(h, w)  # [total, vocab/tp] — vocab-parallel logits
+                return self._cap(o)
+        return self._cap(_linear(h, w))  # [total, vocab/tp] — vocab-parallel logits
+
+    def _cap(self, logits):
+        """Final logit soft-cap (gemma-2), cap * tanh(logits / cap) in the
+        logits' dtype; elementwise, so vocab-parallel shards take it as is."""
+        cap = self.cfg.final_logit_softcap
+        if not cap:
+            return logits
+        return torch.tanh(logits / cap) * cap

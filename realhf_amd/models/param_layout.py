@@ -55,6 +55,8 @@ def tblock_keys(cfg: ReaLModelConfig, layer_idx: int) -> List[str]:
     ks.append(f"{i}.attn.wo.weight")
     if cfg.use_attn_proj_bias:
         ks.append(f"{i}.attn.wo.bias")
+    if cfg.post_norms:  # gemma-2: norm on the attention output
+        ks.append(f"{i}.attn.post_ln.weight")
     ks.append(f"{i}.mlp.ln.weight")
     if cfg.norm_type == "layer":
         ks.append(f"{i}.mlp.ln.bias")
@@ -74,6 +76,8 @@ def tblock_keys(cfg: ReaLModelConfig, layer_idx: int) -> List[str]:
         ks += [f"{i}.mlp.up.weight", f"{i}.mlp.down.weight"]
         if cfg.use_mlp_bias:
             ks += [f"{i}.mlp.up.bias", f"{i}.mlp.down.bias"]
+    if cfg.post_norms:  # gemma-2: norm on the MLP output
+        ks.append(f"{i}.mlp.post_ln.weight")
     return ks
 
 
@@ -146,6 +150,8 @@ def key_full_shape(cfg: ReaLModelConfig, key: str) -> Tuple[int, ...]:
         "attn.wo.bias": (h,),
         "mlp.ln.weight": (h,),
         "mlp.ln.bias": (h,),
+        "attn.post_ln.weight": (h,),
+        "mlp.post_ln.weight": (h,),
         "mlp.gate.weight": (idim, h),
         "mlp.up.weight": (idim, h) if cfg.activation == "silu" else (idim, h),
         "mlp.down.weight": (h, idim),

@@ -8,10 +8,11 @@
 // that slice's dK/dV in MFMA C fragments (16x128 fp32 = 64 VGPR/lane for
 // both).  The workgroup loops over 32-query tiles >= the diagonal:
 //   S^T = K Q^T               (A = K row frag, B = Q row frag)
-//   P^T = exp(S^T*scale - lse[q])
+//   P^T = exp(S^T*scale - lse[q])      (soft-cap: exp(cap*t - lse[q]),
+//                                       t = tanh(S^T*scale / cap))
 //   dV += P^T dO              (A = P^T via LDS, B = dO via tr16)
 //   dP^T = V dO^T             (A = V row frag, B = dO row frag)
-//   dS^T = P^T o (dP^T - D[q]) * scale
+//   dS^T = P^T o (dP^T - D[q]) * scale (soft-cap: * (1 - t^2) too)
 //   dK += dS^T Q              (A = dS^T via LDS, B = Q via tr16)
 //   dQ += dS K  -> fp32 atomics, or (opt-in: max_seqlen given and the
 //                 partials fit) per-kv-block fp32 partials summed in
@@ -85,7 +86,10 @@ __global__ void bw_reduce_dq(const float* __restrict__ part,
 // HD = 256 (gemma): the dK/dV accumulators alone are 128 registers per lane
 // and the tiles take 112 KB of LDS, so that instantiation asks for one
 // workgroup per CU; 64/128 keep two.
-template <int HD, bool DET>
+// CAP = true is the soft-capped form (gemma-2, see attn_varlen.hip); a
+// template parameter because a branch on the argument moved the VGPR count of
+// every uncapped instantiation.
+template <int HD, bool DET, bool CAP = false>
 __global__ __launch_bounds__(64 * BW_WAVES, HD > 128 ? 1 : 2)
 void attn_varlen_bwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
@@ -95,7 +99,8 @@ void attn_varlen_bwd_kernel(
     int n_seqs, float* __restrict__ dq32,
     float* __restrict__ dk32, float* __restrict__ dv32,
     int nq, int nkv, float scale, bool causal, int window,
-    float* __restrict__ dq_part, int nslot, long part_stride) {
+    float* __restrict__ dq_part, int nslot, long part_stride,
+    float softcap, float ncap) {
   constexpr int HDCH = HD / 32;
   const int blk = blockIdx.x;
   if (blk >= blk_offsets[n_seqs]) return;  // over-provisioned grid tail
@@ -198,8 +203,16 @@ void attn_varlen_bwd_kernel(
         const int kidx = k0 + w * 16 + g * 4 + r;
         bool ok = (kidx < L) && (qidx < L) && (!causal || kidx <= qidx)
                   && (window <= 0 || kidx > qidx - window);
-        float p = ok ? __expf(st[qs][r] * scale - lse_s[qs * 16 + i16]) : 0.f;
-        float ds = ok ? p * (dpt[qs][r] - d_s[qs * 16 + i16]) * scale : 0.f;
+        // soft-cap: the score is c = softcap * t with t = tanh(s * scale /
+        // softcap), and dc/ds = (1 - t^2) * scale (exactly 0 at saturation)
+        float sv = st[qs][r] * scale, dsc = scale;
+        if constexpr (CAP) {
+          const float t = softcap_tanh(sv, ncap);
+          sv = softcap * t;
+          dsc = scale * (1.f - t * t);
+        }
+        float p = ok ? __expf(sv - lse_s[qs * 16 + i16]) : 0.f;
+        float ds = ok ? p * (dpt[qs][r] - d_s[qs * 16 + i16]) * dsc : 0.f;
         pt_s[w][g * 4 + r][qs * 16 + i16] = (__bf16)p;
         ds_all[w * 16 + g * 4 + r][qs * 16 + i16] = (__bf16)ds;
       }
@@ -285,8 +298,9 @@ void attn_varlen_bwd_kernel(
 std::vector<torch::Tensor> attn_varlen_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
     torch::Tensor lse, torch::Tensor Dsum, torch::Tensor cu_seqlens,
-    bool causal, double scale, long window, long max_seqlen) {
+    bool causal, double scale, long window, long max_seqlen, double softcap) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(softcap >= 0.0, "attn_varlen_bwd: softcap must be >= 0");
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous() &&
               dout.is_contiguous());
   int total = q.size(0), nq = q.size(1), hd = q.size(2);
@@ -313,8 +327,8 @@ std::vector<torch::Tensor> attn_varlen_bwd(
   dim3 grid((unsigned)(total / BW_KV + bs), nq);
   TORCH_CHECK(hd == 256 || hd == 128 || hd == 64,
               "attn_varlen_bwd: unsupported head_dim ", hd);
-#define BW_LAUNCH(HD_, DET_)                                              \
-  hipLaunchKernelGGL((attn_varlen_bwd_kernel<HD_, DET_>), grid,           \
+#define BW_LAUNCH_(HD_, DET_, CAP_)                                       \
+  hipLaunchKernelGGL((attn_varlen_bwd_kernel<HD_, DET_, CAP_>), grid,     \
     dim3(64 * BW_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
     (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),                 \
     (const bf16*)dout.data_ptr(), lse.data_ptr<float>(),                  \
@@ -322,7 +336,13 @@ std::vector<torch::Tensor> attn_varlen_bwd(
     blk_off.data_ptr<int>(), bs,                                          \
     dq32.data_ptr<float>(), dk32.data_ptr<float>(), dv32.data_ptr<float>(), \
     nq, nkv, (float)scale, causal, (int)window,                           \
-    part_ptr, (int)nslot, part_stride)
+    part_ptr, (int)nslot, part_stride, (float)softcap,                    \
+    softcap_ncap(softcap))
+#define BW_LAUNCH(HD_, DET_)                                              \
+  do {                                                                    \
+    if (softcap > 0.0) BW_LAUNCH_(HD_, DET_, true);                       \
+    else BW_LAUNCH_(HD_, DET_, false);                                    \
+  } while (0)
   if (hd == 256) {
     if (det) BW_LAUNCH(256, true); else BW_LAUNCH(256, false);
   } else if (hd == 128) {
@@ -331,6 +351,7 @@ std::vector<torch::Tensor> attn_varlen_bwd(
     if (det) BW_LAUNCH(64, true); else BW_LAUNCH(64, false);
   }
 #undef BW_LAUNCH
+#undef BW_LAUNCH_
   if (det) {
     const long n4 = part_stride / 4;
     dim3 rgrid((unsigned)((n4 + 255) / 256));

@@ -53,13 +53,20 @@ typedef __attribute__((ext_vector_type(4))) int int4q;
 //   DPL codes from one LDS read.
 // A lane outside [lo, L) never loads its scales (they may be NaN, and
 // 0 * NaN is NaN) and zeroes its tile row (a stale byte can be a NaN code).
-template <int HD, int REP, int W, bool FP8 = false>
+//
+// CAP = true is the soft-capped form (gemma-2): each scaled score becomes
+// softcap * tanh(score / softcap) — for FP8 after k_scale has multiplied it —
+// before the softmax.  A template parameter because a branch on the argument
+// moved the register allocation of 12 of the uncapped instantiations (one
+// gained scratch); it is instantiated for 2 and 4 waves, and a capped request
+// for 8 waves runs with 4.
+template <int HD, int REP, int W, bool FP8 = false, bool CAP = false>
 __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
     const bf16* __restrict__ q, const void* __restrict__ kc,
     const void* __restrict__ vc, const float* __restrict__ kscale,
     const float* __restrict__ vscale, const int* __restrict__ cache_seqlens,
     bf16* __restrict__ out, float* __restrict__ ws, int bs, int nq, int nkv,
-    long maxlen, float scale, int window) {
+    long maxlen, float scale, int window, float softcap, float ncap) {
   constexpr int DPL = HD / WAVE;  // dims per lane (2 for hd=128, 4 for 256)
   using cache_t = std::conditional_t<FP8, unsigned char, __bf16>;
   const int b = blockIdx.x / nkv;
@@ -182,6 +189,13 @@ __global__ __launch_bounds__(64 * W) void attn_decode_kernel(
     }
     #pragma unroll
     for (int r = 0; r < REP; r++) sc[r] *= FP8 ? ks_l : scale;  // q kept raw bf16
+    // soft-cap on the scaled score; lanes outside [lo, L) hold 0 here and
+    // get their -1e30f below
+    if constexpr (CAP) {
+      #pragma unroll
+      for (int r = 0; r < REP; r++)
+        sc[r] = softcap * softcap_tanh(sc[r], ncap);
+    }
     const int nvalid = min(WAVE, r1 - base);
     #pragma unroll
     for (int r = 0; r < REP; r++) {
@@ -313,11 +327,11 @@ __global__ __launch_bounds__(WAVE) void attn_decode_combine_kernel(
 // FP8: kc / vc are e4m3 codes and kscale / vscale their [bs, nkv, maxlen]
 // scales; else bf16 caches and null scales.  Wave count, split heuristic
 // and combine are the same for both.
-template <bool FP8>
-static torch::Tensor attn_decode_impl(
+template <bool FP8, bool CAP>
+static torch::Tensor attn_decode_impl_(
     torch::Tensor q, torch::Tensor kc, torch::Tensor vc, const float* kscale,
     const float* vscale, torch::Tensor cache_seqlens, double scale,
-    long window) {
+    long window, double softcap) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(q.is_contiguous() && kc.is_contiguous() && vc.is_contiguous());
   int bs = q.size(0), nq = q.size(1), hd = q.size(2);
@@ -332,7 +346,9 @@ static torch::Tensor attn_decode_impl(
     return (v == 2 || v == 4 || v == 8) ? v : 4;
   }();
   // W=8 at hd=256 would need 256 KB of LDS: run it with 4
-  const int dec_waves = (hd == 256 && dec_waves_env == 8) ? 4 : dec_waves_env;
+  // (the capped kernels are instantiated for 2 and 4 waves)
+  const int dec_waves =
+      ((hd == 256 || CAP) && dec_waves_env == 8) ? 4 : dec_waves_env;
   // split-K factor: fill the 256-CU chip when bs*nkv is small (decode
   // batches).  Static per shape -> hipGraph-safe; REALHF_AMD_DEC_SPLIT
   // overrides for A/B.
@@ -354,11 +370,11 @@ static torch::Tensor attn_decode_impl(
   auto launch = [&](auto hd_c, auto rep_c) {
     auto go = [&](auto w_c) {
       hipLaunchKernelGGL(
-        (attn_decode_kernel<hd_c.value, rep_c.value, w_c.value, FP8>),
+        (attn_decode_kernel<hd_c.value, rep_c.value, w_c.value, FP8, CAP>),
         grid, dim3(64 * w_c.value), 0, cur_stream(), (const bf16*)q.data_ptr(),
         (const void*)kc.data_ptr(), (const void*)vc.data_ptr(), kscale, vscale,
         (const int*)cs.data_ptr<int>(), (bf16*)out.data_ptr(), ws_ptr, bs, nq,
-        nkv, maxlen, (float)scale, (int)window);
+        nkv, maxlen, (float)scale, (int)window, (float)softcap, softcap_ncap(softcap));
       if (ws_ptr) {
         if (hd_c.value == 256)
           hipLaunchKernelGGL((attn_decode_combine_kernel<256>),
@@ -381,7 +397,9 @@ static torch::Tensor attn_decode_impl(
       // kernels of rep 4 (hd 128) and rep 8 spill to scratch; they are not
       // instantiated and the request runs with 4 waves
       constexpr int hdv = decltype(hd_c)::value, repv = decltype(rep_c)::value;
-      if constexpr (hdv != 256 &&
+      if constexpr (CAP) {
+        // never reached (clamped above); no capped 8-wave kernels
+      } else if constexpr (hdv != 256 &&
                     (!FP8 || repv <= 2 || (hdv == 64 && repv == 4)))
         go(std::integral_constant<int, 8>{});
       else if constexpr (FP8)
@@ -406,11 +424,24 @@ static torch::Tensor attn_decode_impl(
   return out;
 }
 
+template <bool FP8>
+static torch::Tensor attn_decode_impl(
+    torch::Tensor q, torch::Tensor kc, torch::Tensor vc, const float* kscale,
+    const float* vscale, torch::Tensor cache_seqlens, double scale,
+    long window, double softcap) {
+  TORCH_CHECK(softcap >= 0.0, "attn_decode: softcap must be >= 0");
+  if (softcap > 0.0)
+    return attn_decode_impl_<FP8, true>(q, kc, vc, kscale, vscale,
+                                        cache_seqlens, scale, window, softcap);
+  return attn_decode_impl_<FP8, false>(q, kc, vc, kscale, vscale,
+                                       cache_seqlens, scale, window, softcap);
+}
+
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                           torch::Tensor cache_seqlens, double scale,
-                          long window) {
+                          long window, double softcap) {
   return attn_decode_impl<false>(q, kc, vc, nullptr, nullptr, cache_seqlens,
-                                 scale, window);
+                                 scale, window, softcap);
 }
 
 void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
@@ -419,7 +450,7 @@ void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
 torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
                               torch::Tensor kscale, torch::Tensor vcodes,
                               torch::Tensor vscale, torch::Tensor cache_seqlens,
-                              double scale, long window) {
+                              double scale, long window, double softcap) {
   check_fp8_kv_cache(kcodes, kscale, "k");
   check_fp8_kv_cache(vcodes, vscale, "v");
   TORCH_CHECK(kcodes.sizes() == vcodes.sizes());
@@ -429,5 +460,5 @@ torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
               "q [bs, nq, hd], the caches and cache_seqlens must agree");
   return attn_decode_impl<true>(q, kcodes, vcodes, kscale.data_ptr<float>(),
                                 vscale.data_ptr<float>(), cache_seqlens, scale,
-                                window);
+                                window, softcap);
 }

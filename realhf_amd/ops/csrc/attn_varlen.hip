@@ -52,13 +52,20 @@
 // (K 33 KB + V 34 KB + P 18 KB), 64 accumulator VGPRs per lane.  Two KV
 // buffers plus P would be ~156 KB of the 160 KB LDS, so REALHF_AMD_ATTN_DB
 // is ignored at 256.
-template <int HD, bool DB>
+//
+// CAP = true is the soft-capped form (gemma-2): the scaled score becomes
+// softcap * tanh(score / softcap) before the masks.  It is a template
+// parameter and not a branch on the argument because the branch alone moved
+// the register allocation of the uncapped hd=64 kernel (95 -> 96 VGPRs);
+// CAP = false compiles to the code it was.  Instantiated for DB = false only.
+template <int HD, bool DB, bool CAP = false>
 __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k,
     const bf16* __restrict__ v, const int* __restrict__ cu_seqlens,
     const int* __restrict__ blk_offsets, int n_seqs,
     bf16* __restrict__ out, float* __restrict__ lse,
-    int nq, int nkv, float scale, bool causal, int window) {
+    int nq, int nkv, float scale, bool causal, int window,
+    float softcap, float ncap) {
   constexpr int HDCH = HD / 32;  // mfma K-chunks over head_dim
   constexpr int NBUF = DB ? 2 : 1;
   const int blk = blockIdx.x;
@@ -194,6 +201,11 @@ __global__ __launch_bounds__(64 * AV_WAVES, 1) void attn_varlen_fwd_kernel(
         bool ok = (kidx < kv_end) && (!causal || kidx <= qrow) && (qrow < L)
                   && (window <= 0 || kidx > qrow - window);
         float sv = ok ? s_sub[ks][r] * scale : -1e30f;
+        // soft-cap on live scores only: a capped -1e30f sentinel would be
+        // -softcap and pass for a live key in `s_sub > -1e29f` below
+        if constexpr (CAP) {
+          if (ok) sv = softcap * softcap_tanh(sv, ncap);
+        }
         s_sub[ks][r] = sv;
         mx = fmaxf(mx, sv);
       }
@@ -285,9 +297,10 @@ static int attn_db_mode() {
 std::vector<torch::Tensor> attn_varlen_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor cu_seqlens, long max_seqlen, bool causal, double scale,
-    long window) {
+    long window, double softcap) {
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16,
               "attn_varlen_fwd: bf16 only");
+  TORCH_CHECK(softcap >= 0.0, "attn_varlen_fwd: softcap must be >= 0");
   TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
   int total = q.size(0), nq = q.size(1), hd = q.size(2);
   int nkv = k.size(1);
@@ -303,19 +316,24 @@ std::vector<torch::Tensor> attn_varlen_fwd(
   int dbm = attn_db_mode();
   bool use_db = (dbm == 1) || (dbm == -1 && max_seqlen >= 4096);
   TORCH_CHECK(hd == 256 || hd == 128 || hd == 64, "unsupported head_dim ", hd);
-#define FW_LAUNCH(HD_, DB_)                                               \
-  hipLaunchKernelGGL((attn_varlen_fwd_kernel<HD_, DB_>), grid,            \
+#define FW_LAUNCH(HD_, DB_, CAP_)                                         \
+  hipLaunchKernelGGL((attn_varlen_fwd_kernel<HD_, DB_, CAP_>), grid,      \
     dim3(64 * AV_WAVES), 0, cur_stream(), (const bf16*)q.data_ptr(),      \
     (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),                 \
     cu_dev.data_ptr<int>(), blk_off.data_ptr<int>(), bs,                  \
     (bf16*)out.data_ptr(), lse.data_ptr<float>(), nq, nkv, (float)scale,  \
-    causal, (int)window)
-  if (hd == 256) {
-    FW_LAUNCH(256, false);  // single-buffer only (LDS), whatever ATTN_DB says
+    causal, (int)window, (float)softcap,                                  \
+    softcap_ncap(softcap))
+  if (softcap > 0.0) {  // capped form: single-buffer, whatever ATTN_DB says
+    if (hd == 256) FW_LAUNCH(256, false, true);
+    else if (hd == 128) FW_LAUNCH(128, false, true);
+    else FW_LAUNCH(64, false, true);
+  } else if (hd == 256) {
+    FW_LAUNCH(256, false, false);  // single-buffer only (LDS), whatever ATTN_DB says
   } else if (hd == 128) {
-    if (use_db) FW_LAUNCH(128, true); else FW_LAUNCH(128, false);
+    if (use_db) FW_LAUNCH(128, true, false); else FW_LAUNCH(128, false, false);
   } else {
-    if (use_db) FW_LAUNCH(64, true); else FW_LAUNCH(64, false);
+    if (use_db) FW_LAUNCH(64, true, false); else FW_LAUNCH(64, false, false);
   }
 #undef FW_LAUNCH
   CHECK_CUDA_OK();

@@ -32,11 +32,11 @@ void fused_adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                  bool write_bf16);
 torch::Tensor attn_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                           torch::Tensor cache_seqlens, double scale,
-                          long window);
+                          long window, double softcap);
 std::vector<torch::Tensor> attn_varlen_fwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor cu_seqlens, long max_seqlen, bool causal, double scale,
-    long window);
+    long window, double softcap);
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B);
 torch::Tensor tr16_probe(torch::Tensor addr_elem);
 torch::Tensor grouped_gemm(torch::Tensor x, torch::Tensor w,
@@ -53,7 +53,7 @@ torch::Tensor skinny_gemm_nc(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> attn_varlen_bwd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dout,
     torch::Tensor lse, torch::Tensor Dsum, torch::Tensor cu_seqlens,
-    bool causal, double scale, long window, long max_seqlen);
+    bool causal, double scale, long window, long max_seqlen, double softcap);
 int64_t xgmi_create(int64_t rank, int64_t world, int64_t capacity);
 std::vector<py::bytes> xgmi_handles(int64_t h);
 void xgmi_connect(int64_t h, const std::vector<std::string>& data_handles,
@@ -107,7 +107,7 @@ void kv_store_fp8(torch::Tensor k, torch::Tensor v, torch::Tensor kcodes,
 torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
                               torch::Tensor kscale, torch::Tensor vcodes,
                               torch::Tensor vscale, torch::Tensor cache_seqlens,
-                              double scale, long window);
+                              double scale, long window, double softcap);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -125,8 +125,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("slice_intervals", &slice_intervals);
   m.def("set_intervals", &set_intervals);
   m.def("fused_adamw", &fused_adamw);
-  m.def("attn_decode", &attn_decode);
-  m.def("attn_varlen_fwd", &attn_varlen_fwd);
+  // softcap (attention logit soft-cap, gemma-2) trails every attention
+  // binding with default 0.0 = no cap
+  m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k_cache"),
+        py::arg("v_cache"), py::arg("cache_seqlens"), py::arg("scale"),
+        py::arg("window"), py::arg("softcap") = 0.0);
+  m.def("attn_varlen_fwd", &attn_varlen_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("cu_seqlens"), py::arg("max_seqlen"),
+        py::arg("causal"), py::arg("scale"), py::arg("window"),
+        py::arg("softcap") = 0.0);
   m.def("mfma_probe", &mfma_probe);
   m.def("tr16_probe", &tr16_probe);
   m.def("rope_qkv_decode", &rope_qkv_decode);
@@ -139,7 +146,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_varlen_bwd", &attn_varlen_bwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("dout"), py::arg("lse"), py::arg("Dsum"),
         py::arg("cu_seqlens"), py::arg("causal"), py::arg("scale"),
-        py::arg("window"), py::arg("max_seqlen") = 0);
+        py::arg("window"), py::arg("max_seqlen") = 0,
+        py::arg("softcap") = 0.0);
   m.def("xgmi_create", &xgmi_create);
   m.def("xgmi_handles", &xgmi_handles);
   m.def("xgmi_connect", &xgmi_connect);
@@ -155,5 +163,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8_nc", &skinny_gemm_fp8_nc);
   m.def("rope_qkv_decode_fp8", &rope_qkv_decode_fp8);
   m.def("kv_store_fp8", &kv_store_fp8);
-  m.def("attn_decode_fp8", &attn_decode_fp8);
+  m.def("attn_decode_fp8", &attn_decode_fp8, py::arg("q"), py::arg("kcodes"),
+        py::arg("kscale"), py::arg("vcodes"), py::arg("vscale"),
+        py::arg("cache_seqlens"), py::arg("scale"), py::arg("window"),
+        py::arg("softcap") = 0.0);
 }

@@ -38,6 +38,22 @@ DEVINL float wave_max(float x) {
   return __shfl(x, 0, 64);
 }
 
+// Attention logit soft-cap (gemma-2): cap * tanh(x / cap).  No tanhf:
+// tanh(y) = 2 / (1 + e^-2y) - 1 as one v_exp_f32 and one v_rcp_f32 (1 ulp; the
+// denominator is >= 1), with e^(-2x/cap) = 2^(x * ncap) and the host-computed
+// ncap = softcap_ncap(cap) = -2 log2(e) / cap folding three multiplies into
+// one.  It saturates to exactly +-1 — rcp(1) = 1 when the exponential
+// underflows to 0, rcp(inf) = 0 when it overflows — so there is no NaN for
+// any finite score and 1 - t*t is exactly 0 there.  Returns the tanh; callers
+// multiply by cap (the backward also needs 1 - t^2).
+DEVINL float softcap_tanh(float x, float ncap) {
+  return fmaf(2.f, __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * ncap)),
+              -1.f);
+}
+inline float softcap_ncap(double softcap) {
+  return softcap > 0.0 ? (float)(-2.0 * 1.4426950408889634 / softcap) : 0.f;
+}
+
 #define CHECK_CUDA_OK() do { \
   hipError_t e = hipGetLastError(); \
   TORCH_CHECK(e == hipSuccess, "HIP kernel launch failed: ", hipGetErrorString(e)); \

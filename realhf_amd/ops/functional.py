@@ -12,7 +12,10 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        back on torch
   attn_varlen        — flash-attention packed prefill (reference: flash_attn_varlen_func)
   attn_decode        — single-token GQA decode over contiguous KV cache
-                       (reference: flash_attn_with_kvcache)
+                       (reference: flash_attn_with_kvcache); both attention
+                       ops take softcap (gemma-2's logit soft-cap,
+                       cap * tanh(score / cap) before the masks), applied
+                       inside the HIP kernels and by every torch route
   gae                — packed GAE scan (reference: realhf._C.cugae)
   slice_intervals /
   set_intervals      — flat-param interval gather/scatter (realhf._C.interval_op_cuda)
@@ -282,6 +285,14 @@ def geglu(gate_up):
 # ---------------------------------------------------------------------------
 # Attention — packed varlen (prefill/training)
 # ---------------------------------------------------------------------------
+def _softcap(scores: torch.Tensor, softcap: Optional[float]) -> torch.Tensor:
+    """softcap * tanh(scores / softcap) on (unmasked) fp32 scores; None or 0
+    is no cap."""
+    if not softcap:
+        return scores
+    return torch.tanh(scores / softcap) * softcap
+
+
 def attn_varlen_ref(
     q: torch.Tensor,  # [total, nq, hd]
     k: torch.Tensor,  # [total, nkv, hd]
@@ -290,8 +301,10 @@ def attn_varlen_ref(
     causal: bool = True,
     softmax_scale: Optional[float] = None,
     window: Optional[int] = None,  # sliding window incl. self (mistral)
+    softcap: Optional[float] = None,  # logit soft-cap (gemma-2); None/0 = off
 ) -> torch.Tensor:
-    """Per-sequence SDPA in fp32 — the numerics oracle."""
+    """Per-sequence SDPA in fp32 — the numerics oracle.  With softcap the
+    scaled scores become softcap * tanh(scores / softcap) before the masks."""
     nq, hd = q.shape[1], q.shape[2]
     nkv = k.shape[1]
     scale = softmax_scale or (1.0 / math.sqrt(hd))
@@ -307,6 +320,7 @@ def attn_varlen_ref(
             ki = ki.repeat_interleave(rep, dim=0)
             vi = vi.repeat_interleave(rep, dim=0)
         scores = torch.matmul(qi, ki.transpose(-1, -2)) * scale
+        scores = _softcap(scores, softcap)
         L = e - s
         if causal and L > 1:
             mask = torch.triu(
@@ -326,7 +340,8 @@ def attn_varlen_ref(
     return out
 
 
-def _attn_varlen_blocked_torch(q, k, v, cu_seqlens, causal, scale, window=None):
+def _attn_varlen_blocked_torch(q, k, v, cu_seqlens, causal, scale, window=None,
+                               softcap=None):
     """Batched-padded torch implementation on GPU (used for backward
     recompute until the hand-written HIP backward lands): one set of
     batched rocBLAS GEMMs instead of a per-sequence python loop (the loop
@@ -359,6 +374,7 @@ def _attn_varlen_blocked_torch(q, k, v, cu_seqlens, causal, scale, window=None):
         kp = kp.repeat_interleave(rep, dim=1)
         vp = vp.repeat_interleave(rep, dim=1)
     scores = torch.matmul(qp * scale, kp.transpose(-1, -2)).float()
+    scores = _softcap(scores, softcap)
     kpos = torch.arange(Lmax, device=device)
     valid = kpos.unsqueeze(0) < lens.unsqueeze(1)  # [bs, Lmax]
     mask = valid.unsqueeze(1).unsqueeze(2)  # [bs,1,1,L]
@@ -375,16 +391,27 @@ def _attn_varlen_blocked_torch(q, k, v, cu_seqlens, causal, scale, window=None):
     return op[seq_id, local].to(q.dtype)
 
 
+def _check_softcap(softcap: Optional[float]) -> Optional[float]:
+    """None for no cap (None or 0), else the positive float."""
+    if not softcap:
+        return None
+    if softcap < 0:
+        raise ValueError(f"softcap must be positive, got {softcap}")
+    return float(softcap)
+
+
 class _AttnVarlenFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu_seqlens, max_seqlen, causal, scale,
-                window=None):
+                window=None, softcap=None):
         C = _ops.require_hip()
         out, lse = C.attn_varlen_fwd(q, k, v, cu_seqlens, int(max_seqlen),
-                                     causal, scale, int(window or 0))
+                                     causal, scale, int(window or 0),
+                                     float(softcap or 0.0))
         ctx.save_for_backward(q, k, v, out, lse, cu_seqlens)
         ctx.causal, ctx.scale, ctx.max_seqlen = causal, scale, max_seqlen
         ctx.window = window
+        ctx.softcap = softcap
         return out
 
     @staticmethod
@@ -408,6 +435,7 @@ class _AttnVarlenFn(torch.autograd.Function):
                 int(ctx.window or 0),
                 int(ctx.max_seqlen)
                 if os.environ.get("REALHF_AMD_ATTN_BWD_DET") == "1" else 0,
+                float(ctx.softcap or 0.0),
             )
             nq, nkv = q.shape[1], k.shape[1]
             rep = nq // nkv
@@ -416,7 +444,7 @@ class _AttnVarlenFn(torch.autograd.Function):
                 dk32 = dk32.view(t, nkv, rep, -1).sum(2)
                 dv32 = dv32.view(t, nkv, rep, -1).sum(2)
             return (dq32.to(q.dtype), dk32.to(k.dtype), dv32.to(v.dtype),
-                    None, None, None, None, None)
+                    None, None, None, None, None, None)
         # Fallback: blocked recompute with rocBLAS GEMMs (fp32 softmax).
         with torch.enable_grad():
             qg = q.detach().requires_grad_(True)
@@ -424,15 +452,18 @@ class _AttnVarlenFn(torch.autograd.Function):
             vg = v.detach().requires_grad_(True)
             ref = _attn_varlen_blocked_torch(
                 qg, kg, vg, cu_seqlens, ctx.causal, ctx.scale,
-                window=ctx.window,
+                window=ctx.window, softcap=ctx.softcap,
             )
             dq, dk, dv = torch.autograd.grad(ref, (qg, kg, vg), grad_out)
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def attn_varlen(q, k, v, cu_seqlens, max_seqlen, causal=True, softmax_scale=None,
-                window=None):
+                window=None, softcap: Optional[float] = None):
+    """softcap: attention logit soft-cap (gemma-2), applied by every route
+    to the scaled scores before the masks; None or 0 is no cap."""
     scale = softmax_scale or (1.0 / math.sqrt(q.shape[-1]))
+    softcap = _check_softcap(softcap)
     if window is not None and window >= int(max_seqlen):
         window = None  # window wider than any sequence: plain causal
     if (
@@ -442,14 +473,15 @@ def attn_varlen(q, k, v, cu_seqlens, max_seqlen, causal=True, softmax_scale=None
     ):
         return _AttnVarlenFn.apply(
             q.contiguous(), k.contiguous(), v.contiguous(),
-            cu_seqlens, max_seqlen, causal, scale, window,
+            cu_seqlens, max_seqlen, causal, scale, window, softcap,
         )
     if q.is_cuda:
         # odd head dims / dtypes / binding sliding window: batched rocBLAS
         # path (still GPU)
         return _attn_varlen_blocked_torch(q, k, v, cu_seqlens, causal, scale,
-                                          window=window)
-    return attn_varlen_ref(q, k, v, cu_seqlens, causal, scale, window=window)
+                                          window=window, softcap=softcap)
+    return attn_varlen_ref(q, k, v, cu_seqlens, causal, scale, window=window,
+                           softcap=softcap)
 
 
 # ---------------------------------------------------------------------------
@@ -462,6 +494,7 @@ def attn_decode_ref(
     cache_seqlens: torch.Tensor,  # [bs] int32 — valid length INCLUDING new token
     softmax_scale: Optional[float] = None,
     window: Optional[int] = None,
+    softcap: Optional[float] = None,
 ) -> torch.Tensor:
     bs, nq, hd = q.shape
     nkv = k_cache.shape[2]
@@ -478,14 +511,16 @@ def attn_decode_ref(
             vb = vb.repeat_interleave(rep, dim=0)
         qb = q[b].unsqueeze(1).float()  # [nq, 1, hd]
         scores = torch.matmul(qb, kb.transpose(-1, -2)) * scale
+        scores = _softcap(scores, softcap)
         probs = torch.softmax(scores, dim=-1)
         out[b] = torch.matmul(probs, vb).squeeze(1).to(q.dtype)
     return out
 
 
 def attn_decode(q, k_cache, v_cache, cache_seqlens, softmax_scale=None,
-                window=None):
+                window=None, softcap: Optional[float] = None):
     scale = softmax_scale or (1.0 / math.sqrt(q.shape[-1]))
+    softcap = _check_softcap(softcap)
     if window is not None and k_cache.shape[1] <= window:
         window = None  # cache can never exceed the window: plain causal
     hip = (
@@ -498,15 +533,16 @@ def attn_decode(q, k_cache, v_cache, cache_seqlens, softmax_scale=None,
             C = _ops.require_hip()
             return C.attn_decode_fp8(q, k_cache.codes, k_cache.scale,
                                      v_cache.codes, v_cache.scale,
-                                     cache_seqlens, scale, int(window or 0))
+                                     cache_seqlens, scale, int(window or 0),
+                                     softcap or 0.0)
         return attn_decode_fp8_ref(q, k_cache, v_cache, cache_seqlens, scale,
-                                   window=window)
+                                   window=window, softcap=softcap)
     if hip:
         C = _ops.require_hip()
         return C.attn_decode(q, k_cache, v_cache, cache_seqlens, scale,
-                             int(window or 0))
+                             int(window or 0), softcap or 0.0)
     return attn_decode_ref(q, k_cache, v_cache, cache_seqlens, scale,
-                           window=window)
+                           window=window, softcap=softcap)
 
 
 # ---------------------------------------------------------------------------
@@ -1010,7 +1046,8 @@ def fp8_kv_store(k, v, k_cache: Fp8KVCache, v_cache: Fp8KVCache, cu_seqlens,
 
 
 def attn_decode_fp8_ref(q, k_cache: Fp8KVCache, v_cache: Fp8KVCache,
-                        cache_seqlens, softmax_scale=None, window=None):
+                        cache_seqlens, softmax_scale=None, window=None,
+                        softcap=None):
     """attn_decode_ref in fp32 on the dequantized caches, returned in
     q.dtype.  Only the attended positions [lo, L) are dequantized, so
     whatever lies outside them (stale or non-finite) never enters."""
@@ -1027,7 +1064,7 @@ def attn_decode_fp8_ref(q, k_cache: Fp8KVCache, v_cache: Fp8KVCache,
 
         out[b] = attn_decode_ref(
             q[b:b + 1].float(), deq(k_cache), deq(v_cache),
-            torch.tensor([L - lo]), scale)[0]
+            torch.tensor([L - lo]), scale, softcap=softcap)[0]
     return out.to(q.dtype)
 
 
