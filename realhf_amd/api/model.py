@@ -82,6 +82,12 @@ class ReaLModelConfig:
     # norm details
     scale_attn_by_inverse_layer_idx: bool = False
     qk_layernorm: bool = False
+    # qwen3: plain-weight RMSNorm (w, not 1 + w) over head_dim on every q and
+    # every k head, after the QKV bias and before RoPE, eps =
+    # layer_norm_epsilon; one weight [head_dim] for q and one for k per layer
+    # ({i}.attn.q_ln, {i}.attn.k_ln).  Not qk_layernorm, which nothing
+    # implements
+    qk_rmsnorm: bool = False
     # gemma-style sqrt(hidden) embedding scaling
     embedding_multiplier: Optional[float] = None
     # mistral-style sliding-window attention: each token attends to the
@@ -150,6 +156,8 @@ class ReaLModelConfig:
         if self.moe is not None:
             mlp = mlp * self.moe.num_experts + h * self.moe.num_experts
         per_layer = attn + mlp + (4 if self.post_norms else 2) * h
+        if self.qk_rmsnorm:
+            per_layer += 2 * self.head_dim
         emb = v * h
         head = h if self.is_critic else (0 if self.tied_embedding else v * h)
         return emb + self.n_layers * per_layer + head + h

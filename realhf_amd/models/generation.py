@@ -308,6 +308,10 @@ def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str,
         key += (ops.fp8_skinny_enabled(),)
     if kv_quant != "none":
         key += ("kv:" + kv_quant, ops.fp8_kv_enabled())
+    if model.config.qk_rmsnorm:
+        # likewise whether the QK norm runs inside the append kernel or
+        # (REALHF_AMD_NO_QK_NORM_OPS) in torch in front of it
+        key += ("qk_norm", ops.qk_norm_ops_enabled())
     return key
 
 

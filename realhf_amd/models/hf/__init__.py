@@ -254,4 +254,4 @@ def _write_index(save_dir, weight_map):
         json.dump({"metadata": {}, "weight_map": weight_map}, f)
 
 
-from realhf_amd.models.hf import gemma, gemma2, gpt2, llama, mistral, mixtral, qwen2  # noqa: E402,F401
+from realhf_amd.models.hf import gemma, gemma2, gpt2, llama, mistral, mixtral, qwen2, qwen3  # noqa: E402,F401

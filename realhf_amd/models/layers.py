@@ -308,9 +308,24 @@ class ReaLModelBlock(nn.Module):
             orig_max_pos=cfg.max_position_embeddings,
         )
 
+    def _qk_ln(self):
+        """The per-head QK norm weights (qwen3), [hd] each."""
+        i = self.i
+        return (self.p[f"{i}.attn.q_ln.weight"],
+                self.p[f"{i}.attn.k_ln.weight"])
+
     def _rope(self, q, k, rot_len: int, positions):
-        cos, sin = self._rope_tables(rot_len, q.device)
-        interleaved = self.cfg.rotary_interleaved
+        """q and k as attention takes them: RoPE, behind the per-head QK
+        norm where the config has one (one kernel for both)."""
+        cfg = self.cfg
+        cos = sin = None
+        if cfg.apply_rotary:
+            cos, sin = self._rope_tables(rot_len, q.device)
+        interleaved = cfg.rotary_interleaved
+        if cfg.qk_rmsnorm:
+            return ops.qk_norm_rope(q, k, *self._qk_ln(),
+                                    cfg.layer_norm_epsilon, cos, sin,
+                                    positions, interleaved)
         return (ops.apply_rotary(q, cos, sin, positions, interleaved),
                 ops.apply_rotary(k, cos, sin, positions, interleaved))
 
@@ -321,7 +336,7 @@ class ReaLModelBlock(nn.Module):
         prompt K/V into the caches when there are any."""
         cfg = self.cfg
         q, k, v = self._qkv(h, fused_sp=fused_sp)
-        if cfg.apply_rotary:
+        if cfg.apply_rotary or cfg.qk_rmsnorm:
             # graph-capture-safe length bound: never read positions back
             if k_cache is not None:
                 # generation prefill: use the SESSION's cache length so
@@ -381,7 +396,7 @@ class ReaLModelBlock(nn.Module):
         torch, then ops.attn_decode."""
         cfg = self.cfg
         q, k, v = self._qkv(h, fp8=self.fp8.get("qkv"))
-        if cfg.apply_rotary:
+        if cfg.apply_rotary or cfg.qk_rmsnorm:
             # graph-capture-safe length bound: never read positions back
             q, k = self._rope(q, k, int(k_cache.shape[1]), positions)
         bs = k_cache.shape[0]
@@ -421,13 +436,35 @@ class ReaLModelBlock(nn.Module):
         """The fused decode epilogue, one kernel for qkv-split + bias + RoPE
         + KV append: returns q [bs, nq, hd] and writes the new K/V rows at
         cache_seqlens - 1.  qkv_raw is bf16 or split-K slabs."""
+        cfg = self.cfg
         cos, sin = self._rope_tables(int(k_cache.shape[1]), qkv_raw.device)
-        tail = (cache_seqlens, cos, sin, self.nq, self.cfg.apply_rotary)
+        tail = (cache_seqlens, cos, sin, self.nq, cfg.apply_rotary)
+        bf16_form, fp8_form = C.rope_qkv_decode, C.rope_qkv_decode_fp8
+        if cfg.qk_rmsnorm and ops.qk_norm_ops_enabled():
+            # qwen3: the same launch with the per-head QK norm between the
+            # bias add and RoPE
+            bf16_form, fp8_form = (C.rope_qkv_decode_norm,
+                                   C.rope_qkv_decode_fp8_norm)
+            tail += (*self._qk_ln(), cfg.layer_norm_epsilon)
+        elif cfg.qk_rmsnorm:
+            # REALHF_AMD_NO_QK_NORM_OPS=1, the A/B baseline and test oracle:
+            # qkv_raw is bf16 here (_fused_decode asks for no slabs); bias
+            # and the norm of the q and k head rows in torch, then the
+            # un-normed epilogue
+            if bias is not None:
+                qkv_raw, bias = qkv_raw + bias, None
+            nqk = self.nq + self.nkv
+            rows = qkv_raw.reshape(qkv_raw.shape[0], -1, self.hd)
+            q_w, k_w = self._qk_ln()
+            w = torch.cat([q_w.expand(self.nq, -1), k_w.expand(self.nkv, -1)])
+            qkv_raw = torch.cat(
+                [ops.rms_norm_ref(rows[:, :nqk], w, cfg.layer_norm_epsilon),
+                 rows[:, nqk:]], dim=1).view(qkv_raw.shape)
         if not isinstance(k_cache, ops.Fp8KVCache):
-            return C.rope_qkv_decode(qkv_raw, bias, k_cache, v_cache, *tail)
+            return bf16_form(qkv_raw, bias, k_cache, v_cache, *tail)
         if ops.fp8_kv_enabled():
             # the same epilogue, quantizing the K and V head rows
-            return C.rope_qkv_decode_fp8(
+            return fp8_form(
                 qkv_raw, bias, k_cache.codes, k_cache.scale,
                 v_cache.codes, v_cache.scale, *tail)
         # REALHF_AMD_NO_FP8_KV=1, the A/B baseline and test oracle: the
@@ -437,7 +474,7 @@ class ReaLModelBlock(nn.Module):
         # ops.attn_decode then takes the reference
         ks, vs = (torch.empty(k_cache.shape, dtype=torch.bfloat16,
                               device=qkv_raw.device) for _ in range(2))
-        q = C.rope_qkv_decode(qkv_raw, bias, ks, vs, *tail)
+        q = bf16_form(qkv_raw, bias, ks, vs, *tail)
         idx = (cache_seqlens.long() - 1).clamp(min=0)
         b_idx = torch.arange(ks.shape[0], device=ks.device)
         ops.fp8_kv_append_ref(ks[b_idx, idx], vs[b_idx, idx],
@@ -457,7 +494,10 @@ class ReaLModelBlock(nn.Module):
         qkv_dim = (self.nq + 2 * self.nkv) * self.hd
         merged = _maybe_merged(self.p, self._qkv_names, qkv_dim)
         if merged is not None:
-            qkv_raw, _ = _decode_linear(h, merged, fp8.get("qkv"), slabs=True)
+            # the torch QK norm of REALHF_AMD_NO_QK_NORM_OPS=1 needs summed rows
+            qkv_raw, _ = _decode_linear(
+                h, merged, fp8.get("qkv"),
+                slabs=not cfg.qk_rmsnorm or ops.qk_norm_ops_enabled())
         else:
             qkv_raw = torch.cat(
                 [_linear(h, self.p[n]) for n in self._qkv_names], dim=-1)
@@ -585,15 +625,19 @@ class OutputHead(nn.Module):
     def forward(self, x):
         cfg = self.cfg
         h = _norm(cfg, x, self.p[f"{self.i}.ln_f.weight"], self.p.get(f"{self.i}.ln_f.bias"))
-        if constants.has_current() and constants.sequence_parallel():
-            h = mappings.gather_from_sp_region(h)
+        sp = constants.has_current() and constants.sequence_parallel()
         w = self.tied_w if self.tied_w is not None else self.p.get(f"{self.i}.head.weight")
+        tp = constants.tp_world_size() if constants.has_current() else 1
+        if not cfg.is_critic and tp > 1 and torch.is_grad_enabled():
+            # fused (copy-to-TP | SP-gather) + GEMM on the PRE-mapping h: bwd
+            # all-reduce (SP: reduce-scatter) overlaps dW.  Under SP an
+            # explicit gather in front of the copy-to-TP form would sum the
+            # input grad over tp twice: all-reduce, then reduce-scatter
+            return self._cap(mappings.column_parallel_linear(h, w, sp))
+        if sp:
+            h = mappings.gather_from_sp_region(h)
         if cfg.is_critic:
             return _linear(h.float(), w.float())  # [total, 1] fp32
-        tp = constants.tp_world_size() if constants.has_current() else 1
-        if tp > 1 and torch.is_grad_enabled():
-            # fused copy-to-TP + GEMM: bwd all-reduce overlaps dW
-            return self._cap(mappings.column_parallel_linear(h, w, False))
         h = mappings.copy_to_tp_region(h)
         if not torch.is_grad_enabled():
             # decode: the vocab head streams 262 MB of weights per token —

@@ -55,6 +55,9 @@ def tblock_keys(cfg: ReaLModelConfig, layer_idx: int) -> List[str]:
     ks.append(f"{i}.attn.wo.weight")
     if cfg.use_attn_proj_bias:
         ks.append(f"{i}.attn.wo.bias")
+    if cfg.qk_rmsnorm:  # qwen3: per-head norms on q and k; after wo, so
+        # that wq/wk/wv stay adjacent (merged QKV view)
+        ks += [f"{i}.attn.q_ln.weight", f"{i}.attn.k_ln.weight"]
     if cfg.post_norms:  # gemma-2: norm on the attention output
         ks.append(f"{i}.attn.post_ln.weight")
     ks.append(f"{i}.mlp.ln.weight")
@@ -129,6 +132,14 @@ def key_kind(key: str) -> str:
     return REPLICATED
 
 
+def grad_is_head_partial(key: str) -> bool:
+    """REPLICATED keys whose gradient on a TP rank is a partial sum over that
+    rank's heads (the per-head q/k norm weights): it must be summed over the
+    TP group with or without sequence parallelism, where every other
+    replicated gradient is a partial sum only under SP."""
+    return key.split(".", 1)[1] in ("attn.q_ln.weight", "attn.k_ln.weight")
+
+
 def key_full_shape(cfg: ReaLModelConfig, key: str) -> Tuple[int, ...]:
     h = cfg.hidden_dim
     name = key.split(".", 1)[1]
@@ -148,6 +159,8 @@ def key_full_shape(cfg: ReaLModelConfig, key: str) -> Tuple[int, ...]:
         "attn.wv.bias": (kvd,),
         "attn.wo.weight": (h, qd),
         "attn.wo.bias": (h,),
+        "attn.q_ln.weight": (cfg.head_dim,),
+        "attn.k_ln.weight": (cfg.head_dim,),
         "mlp.ln.weight": (h,),
         "mlp.ln.bias": (h,),
         "attn.post_ln.weight": (h,),

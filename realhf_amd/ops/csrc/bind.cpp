@@ -108,6 +108,31 @@ torch::Tensor attn_decode_fp8(torch::Tensor q, torch::Tensor kcodes,
                               torch::Tensor kscale, torch::Tensor vcodes,
                               torch::Tensor vscale, torch::Tensor cache_seqlens,
                               double scale, long window, double softcap);
+// Per-head QK RMSNorm (qwen3) fused with RoPE: training / prefill forward
+// {q', k', rstd} and backward {dq, dk, dq_w, dk_w}; q and k may be strided
+// views into the merged QKV output.  The decode epilogues with the norm
+// between bias and RoPE take the arguments of the un-normed pair plus
+// q_w, k_w, eps
+std::vector<torch::Tensor> qk_norm_rope_fwd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor q_w, torch::Tensor k_w,
+    double eps, torch::Tensor cosb, torch::Tensor sinb,
+    torch::Tensor positions, bool apply_rope);
+std::vector<torch::Tensor> qk_norm_rope_bwd(
+    torch::Tensor dq_out, torch::Tensor dk_out, torch::Tensor q,
+    torch::Tensor k, torch::Tensor q_w, torch::Tensor k_w, torch::Tensor rstd,
+    torch::Tensor cosb, torch::Tensor sinb, torch::Tensor positions,
+    bool apply_rope);
+torch::Tensor rope_qkv_decode_norm(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
+    torch::Tensor vcache, torch::Tensor cache_seqlens, torch::Tensor cosb,
+    torch::Tensor sinb, long nq, bool apply_rope, torch::Tensor q_w,
+    torch::Tensor k_w, double eps);
+torch::Tensor rope_qkv_decode_fp8_norm(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
+    torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope, torch::Tensor q_w, torch::Tensor k_w,
+    double eps);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -167,4 +192,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kscale"), py::arg("vcodes"), py::arg("vscale"),
         py::arg("cache_seqlens"), py::arg("scale"), py::arg("window"),
         py::arg("softcap") = 0.0);
+  m.def("qk_norm_rope_fwd", &qk_norm_rope_fwd);
+  m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd);
+  m.def("rope_qkv_decode_norm", &rope_qkv_decode_norm);
+  m.def("rope_qkv_decode_fp8_norm", &rope_qkv_decode_fp8_norm);
 }

@@ -36,6 +36,16 @@ DEVINL float group_max(float x) {
   return x;
 }
 
+// sum over the same group, same condition (the per-head QK RMSNorm's sum of
+// squares); every lane of the group gets the same bits: the butterfly adds
+// the same pairs in every lane
+template <int G>
+DEVINL float group_sum(float x) {
+  #pragma unroll
+  for (int off = 1; off < G; off <<= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
 // Decode.  e4m3 -> f32 by v_cvt_pk_f32_fp8 is exact (subnormals included);
 // the upper 16 bits of that f32 are the same value as a bf16, exactly: an
 // e4m3 value has 3 mantissa bits and bf16 keeps 7.

@@ -17,11 +17,18 @@
 // items of a head take its amax by shfl_xor.  That group is always inside
 // one wave and leaves the grid-stride loop together: the block is 256
 // threads, hd/8 is 8, 16 or 32, and nwork is a multiple of it.
+//
+// NORM mode (qwen3's per-head QK RMSNorm): after the slab sum and the bias
+// add and before RoPE, a q or k head row is scaled by rstd * w[d], rstd over
+// the head's hd elements in fp32 — the sum of squares goes over the same
+// hd/8-lane group as the FP8 amax (group_sum).  V heads run the shuffles and
+// drop the result.  The head dim to normalise over is a template argument
+// (0 = no norm), like FP8_HD: the un-normed forms keep their code.
 #include "common.h"
 #include "fp8_e4m3.h"
 #include "slab_sum.h"
 
-template <bool SLAB, int FP8_HD = 0>
+template <bool SLAB, int FP8_HD = 0, int NORM_HD = 0>
 __global__ __launch_bounds__(256) void rope_qkv_decode_kernel(
     const void* __restrict__ qkv_in,  // bf16 [bs, qkvd] | fp32 [nks, bs, qkvd]
     const bf16* __restrict__ bias,  // [(nq+2nkv)*hd] or null
@@ -33,7 +40,9 @@ __global__ __launch_bounds__(256) void rope_qkv_decode_kernel(
     const int* __restrict__ cache_seqlens,  // [bs]
     const float* __restrict__ cosb, const float* __restrict__ sinb,  // [*, hd/2]
     int bs, int nq, int nkv, int hd, long maxlen, long qkv_stride,
-    bool apply_rope, int nks) {
+    bool apply_rope, int nks,
+    const bf16* __restrict__ q_w = nullptr,  // NORM: [hd] each, else unused
+    const bf16* __restrict__ k_w = nullptr, float eps = 0.f) {
   const int nh = nq + 2 * nkv;
   const int hd2 = hd / 2;
   const long nwork = (long)bs * nh * (hd2 / 4);
@@ -57,6 +66,13 @@ __global__ __launch_bounds__(256) void rope_qkv_decode_kernel(
     if (apply_rope) {
       c = *(const float4v*)(cosb + (long)pos * hd2 + d0);
       s = *(const float4v*)(sinb + (long)pos * hd2 + d0);
+    }
+    short4v w1 = {}, w2 = {};
+    if constexpr (NORM_HD != 0) {
+      // V heads load k_w and ignore it
+      const short* w = (const short*)(h < nq ? q_w : k_w);
+      w1 = *(const short4v*)(w + d0);
+      w2 = *(const short4v*)(w + hd2 + d0);
     }
     float4v f1, f2;
     if constexpr (SLAB) {
@@ -83,6 +99,25 @@ __global__ __launch_bounds__(256) void rope_qkv_decode_kernel(
       for (int j = 0; j < 4; j++) {
         f1[j] += __bfloat162float(((const bf16*)&b1)[j]);
         f2[j] += __bfloat162float(((const bf16*)&b2)[j]);
+      }
+    }
+    if constexpr (NORM_HD != 0) {
+      float ss = 0.f;
+      #pragma unroll
+      for (int j = 0; j < 4; j++) {
+        // explicit fmas: every form (slab or not, FP8 cache or not) rounds
+        // the sum alike, whatever the compiler would contract
+        ss = fmaf(f1[j], f1[j], ss);
+        ss = fmaf(f2[j], f2[j], ss);
+      }
+      ss = group_sum<NORM_HD / 8>(ss);
+      const float rs = rsqrtf(fmaf(ss, 1.f / NORM_HD, eps));
+      if (h < nq + nkv) {
+        #pragma unroll
+        for (int j = 0; j < 4; j++) {
+          f1[j] *= rs * bf2f(w1[j]);
+          f2[j] *= rs * bf2f(w2[j]);
+        }
       }
     }
     bf16* dst;
@@ -146,9 +181,11 @@ static torch::Tensor rope_qkv_decode_impl(
     torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
     torch::Tensor vcache, float* kscale, float* vscale,
     torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
-    long nq, bool apply_rope) {
+    long nq, bool apply_rope, const torch::Tensor* q_w = nullptr,
+    const torch::Tensor* k_w = nullptr, double eps = 0.0) {
   TORCH_CHECK(qkv.is_cuda());
   const bool fp8 = kscale != nullptr;
+  const bool norm = q_w != nullptr;
   const bool slab = qkv.dim() == 3;  // fp32 split-K partials [nks, bs, qkvd]
   if (slab) {
     TORCH_CHECK(qkv.scalar_type() == torch::kFloat && qkv.is_contiguous());
@@ -170,15 +207,42 @@ static torch::Tensor rope_qkv_decode_impl(
   const bf16* bptr = nullptr;
   if (bias.has_value()) bptr = (const bf16*)bias->data_ptr();
   long qkv_stride = slab ? qkv.stride(1) : qkv.stride(0);
+  const bf16* qw = nullptr;
+  const bf16* kw = nullptr;
+  if (norm) {
+    for (const torch::Tensor* w : {q_w, k_w})
+      TORCH_CHECK(w->is_cuda() && w->scalar_type() == torch::kBFloat16 &&
+                  w->dim() == 1 && w->size(0) == hd && w->is_contiguous(),
+                  "qk norm weights must be contiguous bf16 [head_dim]");
+    qw = (const bf16*)q_w->data_ptr();
+    kw = (const bf16*)k_w->data_ptr();
+  }
   auto launch = [&](auto kern, int nks_arg) {
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, cur_stream(),
       (const void*)qkv.data_ptr(), bptr, (bf16*)q_out.data_ptr(),
       kcache.data_ptr(), vcache.data_ptr(), kscale, vscale,
       (const int*)cache_seqlens.data_ptr<int>(),
       (const float*)cosb.data_ptr<float>(), (const float*)sinb.data_ptr<float>(),
-      bs, (int)nq, nkv, hd, maxlen, qkv_stride, apply_rope, nks_arg);
+      bs, (int)nq, nkv, hd, maxlen, qkv_stride, apply_rope, nks_arg,
+      qw, kw, (float)eps);
   };
-  if (!fp8) {
+  if (norm) {
+    // NORM forms: hd is compile-time for the group reduction, FP8 or not
+    auto pick = [&](auto hdc) {
+      constexpr int HD = decltype(hdc)::value;
+      if (fp8) {
+        if (slab) launch(rope_qkv_decode_kernel<true, HD, HD>, nks);
+        else launch(rope_qkv_decode_kernel<false, HD, HD>, 1);
+      } else {
+        if (slab) launch(rope_qkv_decode_kernel<true, 0, HD>, nks);
+        else launch(rope_qkv_decode_kernel<false, 0, HD>, 1);
+      }
+    };
+    if (hd == 64) pick(std::integral_constant<int, 64>{});
+    else if (hd == 128) pick(std::integral_constant<int, 128>{});
+    else if (hd == 256) pick(std::integral_constant<int, 256>{});
+    else TORCH_CHECK(false, "qk norm decode: unsupported head_dim ", hd);
+  } else if (!fp8) {
     if (slab) launch(rope_qkv_decode_kernel<true>, nks);
     else launch(rope_qkv_decode_kernel<false>, 1);
   } else if (hd == 64) {
@@ -205,6 +269,18 @@ torch::Tensor rope_qkv_decode(
                               cache_seqlens, cosb, sinb, nq, apply_rope);
 }
 
+// rope_qkv_decode with the per-head QK RMSNorm (q_w, k_w bf16 [hd], eps)
+// between the bias add and RoPE
+torch::Tensor rope_qkv_decode_norm(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcache,
+    torch::Tensor vcache, torch::Tensor cache_seqlens, torch::Tensor cosb,
+    torch::Tensor sinb, long nq, bool apply_rope, torch::Tensor q_w,
+    torch::Tensor k_w, double eps) {
+  return rope_qkv_decode_impl(qkv, bias, kcache, vcache, nullptr, nullptr,
+                              cache_seqlens, cosb, sinb, nq, apply_rope, &q_w,
+                              &k_w, eps);
+}
+
 // codes [bs, maxlen, nkv, hd] (one byte per element), scale fp32
 // [bs, nkv, maxlen]; everything else as rope_qkv_decode
 void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
@@ -220,11 +296,12 @@ void check_fp8_kv_cache(const torch::Tensor& codes, const torch::Tensor& scale,
               what, " scale must be contiguous fp32 [bs, nkv, maxlen]");
 }
 
-torch::Tensor rope_qkv_decode_fp8(
+static torch::Tensor rope_qkv_decode_fp8_impl(
     torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
     torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
     torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
-    long nq, bool apply_rope) {
+    long nq, bool apply_rope, const torch::Tensor* q_w = nullptr,
+    const torch::Tensor* k_w = nullptr, double eps = 0.0) {
   check_fp8_kv_cache(kcodes, kscale, "k");
   check_fp8_kv_cache(vcodes, vscale, "v");
   TORCH_CHECK(kcodes.sizes() == vcodes.sizes());
@@ -234,5 +311,25 @@ torch::Tensor rope_qkv_decode_fp8(
   return rope_qkv_decode_impl(qkv, bias, kcodes, vcodes,
                               kscale.data_ptr<float>(),
                               vscale.data_ptr<float>(), cache_seqlens, cosb,
-                              sinb, nq, apply_rope);
+                              sinb, nq, apply_rope, q_w, k_w, eps);
+}
+
+torch::Tensor rope_qkv_decode_fp8(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
+    torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope) {
+  return rope_qkv_decode_fp8_impl(qkv, bias, kcodes, kscale, vcodes, vscale,
+                                  cache_seqlens, cosb, sinb, nq, apply_rope);
+}
+
+torch::Tensor rope_qkv_decode_fp8_norm(
+    torch::Tensor qkv, c10::optional<torch::Tensor> bias, torch::Tensor kcodes,
+    torch::Tensor kscale, torch::Tensor vcodes, torch::Tensor vscale,
+    torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
+    long nq, bool apply_rope, torch::Tensor q_w, torch::Tensor k_w,
+    double eps) {
+  return rope_qkv_decode_fp8_impl(qkv, bias, kcodes, kscale, vcodes, vscale,
+                                  cache_seqlens, cosb, sinb, nq, apply_rope,
+                                  &q_w, &k_w, eps);
 }

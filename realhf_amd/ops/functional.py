@@ -5,6 +5,10 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        gemma_style=True is the same kernels in their 1 + w
                        weight mode
   apply_rotary       — RoPE on packed varlen qk (reference: flash-attn fused rotary)
+  qk_norm_rope       — per-head QK RMSNorm (qwen3) + RoPE on q and k in one
+                       kernel fwd/bwd, reading q/k in place from the QKV
+                       GEMM output; REALHF_AMD_NO_QK_NORM_OPS=1 puts the
+                       norm back on torch (qk_norm_rope_ref)
   swiglu             — silu(gate)*up fused fwd/bwd
   geglu              — gelu_tanh(gate)*up fused fwd/bwd (gemma), the swiglu
                        kernels with the activation as a template parameter;
@@ -216,6 +220,87 @@ def apply_rotary(x, cos, sin, positions, interleaved=False):
     if _ops.use_hip(x):
         return _RotaryFn.apply(x.contiguous(), cos, sin, positions, interleaved)
     return apply_rotary_ref(x, cos, sin, positions, interleaved)
+
+
+# ---------------------------------------------------------------------------
+# Per-head QK RMSNorm + RoPE (qwen3)
+# ---------------------------------------------------------------------------
+# head dims the fused kernels are instantiated for
+QK_NORM_HEAD_DIMS = (64, 128, 256)
+
+
+def qk_norm_ops_enabled() -> bool:
+    """The per-head QK RMSNorm runs inside the HIP kernels (qk_norm_rope,
+    rope_qkv_decode_norm) unless REALHF_AMD_NO_QK_NORM_OPS=1 (read at call
+    time), which puts the norm back on torch in front of the un-normed
+    kernels: the A/B baseline for tests/test_qwen3_gpu.py and
+    tools/bench_qk_norm.py."""
+    return os.environ.get("REALHF_AMD_NO_QK_NORM_OPS") != "1"
+
+
+def qk_norm_rope_ref(q, k, q_w, k_w, eps, cos, sin, positions,
+                     interleaved=False):
+    """fp32 torch: plain-weight RMSNorm over head_dim on every q and k head
+    row [total, heads, hd], then apply_rotary_ref (cos None: no rotation)."""
+
+    def one(x, w):
+        xf = x.float()
+        n = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+        if cos is not None:
+            n = apply_rotary_ref(n, cos, sin, positions, interleaved)
+        return n.to(x.dtype)
+
+    return one(q, q_w), one(k, k_w)
+
+
+class _QKNormRopeFn(torch.autograd.Function):
+    """One launch forward (q and k, norm + RoPE) and one backward; q and k are
+    saved as they came, normally views into the QKV GEMM output."""
+
+    @staticmethod
+    def forward(ctx, q, k, q_w, k_w, eps, cos, sin, positions):
+        C = _ops.require_hip()
+        rope = cos is not None
+        if not rope:  # unused by the kernels
+            cos = sin = positions = q.new_empty(0, dtype=torch.float32)
+        q_out, k_out, rstd = C.qk_norm_rope_fwd(q, k, q_w, k_w, eps, cos, sin,
+                                                positions, rope)
+        ctx.save_for_backward(q, k, q_w, k_w, rstd, cos, sin, positions)
+        ctx.rope = rope
+        return q_out, k_out
+
+    @staticmethod
+    def backward(ctx, dq_out, dk_out):
+        C = _ops.require_hip()
+        q, k, q_w, k_w, rstd, cos, sin, positions = ctx.saved_tensors
+        dq, dk, dqw, dkw = C.qk_norm_rope_bwd(
+            dq_out.contiguous(), dk_out.contiguous(), q, k, q_w, k_w, rstd,
+            cos, sin, positions, ctx.rope)
+        return dq, dk, dqw, dkw, None, None, None, None
+
+
+def _qk_rows(x):
+    """x [total, heads, hd] as the kernels take it: unit stride inside a head
+    row and from head to head; the token stride is free."""
+    if x.stride(2) == 1 and (x.shape[1] == 1 or x.stride(1) == x.shape[2]) \
+            and x.stride(0) % 4 == 0 and x.data_ptr() % 8 == 0:
+        return x
+    return x.contiguous()
+
+
+def qk_norm_rope(q, k, q_w, k_w, eps, cos, sin, positions, interleaved=False):
+    """q' = rope(rmsnorm_head(q) * q_w), k' likewise with k_w; q [total, nq,
+    hd], k [total, nkv, hd], weights [hd], cos = None skips the rotation.  On
+    the GPU one HIP kernel forward and one backward, reading q and k in place
+    when they are views into the merged QKV output; interleaved rotary, a
+    head dim outside QK_NORM_HEAD_DIMS, fp32, the CPU and
+    REALHF_AMD_NO_QK_NORM_OPS=1 take qk_norm_rope_ref."""
+    if (_ops.use_hip(q) and qk_norm_ops_enabled() and not interleaved
+            and q.shape[-1] in QK_NORM_HEAD_DIMS and q.element_size() == 2):
+        return _QKNormRopeFn.apply(_qk_rows(q), _qk_rows(k), q_w, k_w, eps,
+                                   cos, sin, positions)
+    return qk_norm_rope_ref(q, k, q_w, k_w, eps, cos, sin, positions,
+                            interleaved)
 
 
 # ---------------------------------------------------------------------------

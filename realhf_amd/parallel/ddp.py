@@ -108,7 +108,10 @@ class ZeRO1Optimizer:
         # not tp x (they are discounted by 1/tp before the model-group
         # norm reduction below).
         self._repl_ivs = []  # flat intervals of replicated params
-        self._sp_repl_ivs = []  # same, but only when SP needs the tp-sum
+        # the intervals step() sums over tp, each exactly once: under SP all
+        # of _repl_ivs; without SP only those whose grads are partial sums
+        # over a rank's heads (PL.grad_is_head_partial: qwen3's q/k norms)
+        self._sp_repl_ivs = []
         self.tp_group = None
         self.tp_size = g.tp_size if g is not None else 1
         self.pp_size = g.pp_size if g is not None else 1
@@ -125,6 +128,8 @@ class ZeRO1Optimizer:
                 if kind == PL.REPLICATED:
                     sp_ = model.layout.specs[k]
                     self._repl_ivs.append((sp_.start, sp_.end))
+                    if PL.grad_is_head_partial(k):
+                        self._sp_repl_ivs.append((sp_.start, sp_.end))
             if constants.has_current() and constants.sequence_parallel():
                 self._sp_repl_ivs = list(self._repl_ivs)
 
@@ -495,7 +500,8 @@ class ZeRO1Optimizer:
         cfg = self.cfg
         dev = self.model.flat_param.device
 
-        # 0. SP: sum replicated params' grads over the tp group
+        # 0. sum over the tp group the replicated params' grads that are
+        #    per-rank partials (SP: all of them; else the head-partial ones)
         if self._sp_repl_ivs:
             for a, b in self._sp_repl_ivs:
                 dist.all_reduce(self.grad_padded[a:b], group=self.tp_group)

@@ -21,6 +21,7 @@ SRC = [
     "realhf_amd/ops/csrc/interval.hip",
     "realhf_amd/ops/csrc/attn_decode.hip",
     "realhf_amd/ops/csrc/rope_decode.hip",
+    "realhf_amd/ops/csrc/qk_norm_rope.hip",
     "realhf_amd/ops/csrc/grouped_gemm.hip",
     "realhf_amd/ops/csrc/skinny_gemm.hip",
     "realhf_amd/ops/csrc/attn_varlen.hip",
