@@ -312,6 +312,10 @@ def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str,
         # likewise whether the QK norm runs inside the append kernel or
         # (REALHF_AMD_NO_QK_NORM_OPS) in torch in front of it
         key += ("qk_norm", ops.qk_norm_ops_enabled())
+    if model.config.moe is not None:
+        # likewise whether MoE layers decode on the moe_decode kernels or
+        # (REALHF_AMD_NO_MOE_DECODE) on the training route, which no graph holds
+        key += ("moe_decode", ops.moe_decode_enabled())
     return key
 
 
@@ -352,6 +356,17 @@ def decode_graph_supported(cfg, dtype, device) -> bool:
     what hipGraph capture needs: the torch fallback for other head dims or
     dtypes reads cache_seqlens on the host."""
     return ops.hip_attn_supported(dtype, cfg.head_dim, device)
+
+
+def moe_decode_graph_supported(model, bs: int) -> bool:
+    """Does every MoE layer of the model run its decode step on the
+    moe_decode kernels (no host sync) at this batch size?"""
+    from realhf_amd.models.moe import MoELayer
+
+    layers = [m for m in model.modules() if isinstance(m, MoELayer)]
+    return (bs <= ops.MOE_DECODE_MAX_ROWS and bool(layers)
+            and all(m.decode_supported(model.dtype, model.device)
+                    for m in layers))
 
 
 @torch.no_grad()
@@ -446,10 +461,13 @@ def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
         and decode_graph_supported(cfg, model.dtype, device)
         # MoE dispatch reads expert counts on the host (counts.cpu());
         # a D2H sync inside stream capture DEADLOCKS rather than erroring.
-        # pad_to_capacity makes counts compile-time constants (no sync) —
-        # graph capture of MoE decode is then possible, but stays opt-in
+        # The moe_decode kernels have no sync: a MoE model under their gate
+        # captures like a dense one.  Otherwise pad_to_capacity makes
+        # counts compile-time constants (no sync) — graph capture of MoE
+        # decode is then possible, but stays opt-in
         # (REALHF_AMD_MOE_GRAPH=1) until validated on hardware.
         and (cfg.moe is None
+             or moe_decode_graph_supported(model, bs)
              or (cfg.moe.pad_to_capacity
                  and os.environ.get("REALHF_AMD_MOE_GRAPH") == "1"))
         # an FP8 KV cache under REALHF_AMD_NO_FP8_KV=1 goes through the torch

@@ -297,7 +297,7 @@ class ReaLModelBlock(nn.Module):
                                          v_cache, cache_seqlens)
         # prefill and training never read the quantized weights
         return self._attn_epilogue(x, attn_out, sp,
-                                   self.fp8 if decode else {})
+                                   self.fp8 if decode else {}, decode)
 
     def _rope_tables(self, rot_len: int, device):
         cfg = self.cfg
@@ -411,9 +411,9 @@ class ReaLModelBlock(nn.Module):
         return ops.attn_decode(q, k_cache, v_cache, cache_seqlens, scale,
                                window=self.window, softcap=self.softcap)
 
-    def _attn_epilogue(self, x, attn_out, sp, fp8):
+    def _attn_epilogue(self, x, attn_out, sp, fp8, decode=False):
         """wo (+ LoRA delta), SP/TP reduce, bias, (post norm,) residual, MLP:
-        the tail of the two non-fused routes."""
+        the tail of the two non-fused routes (decode: the eager decode one)."""
         i = self.i
         cfg = self.cfg
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
@@ -430,7 +430,7 @@ class ReaLModelBlock(nn.Module):
             o = o + self.p[f"{i}.attn.wo.bias"]
         if cfg.post_norms:  # after the TP reduce: the norm needs whole rows
             o = _norm(cfg, o, self.p[f"{i}.attn.post_ln.weight"], None)
-        return self._mlp(x + o, sp, fp8=fp8)
+        return self._mlp(x + o, sp, fp8=fp8, decode=decode)
 
     def _rope_append(self, C, qkv_raw, bias, k_cache, v_cache, cache_seqlens):
         """The fused decode epilogue, one kernel for qkv-split + bias + RoPE
@@ -512,11 +512,17 @@ class ReaLModelBlock(nn.Module):
                                    softcap=self.softcap)
         attn_out = attn_out.reshape(attn_out.shape[0], self.nq * self.hd)
         # fused (x + o) + mlp-norm: plain RMS, or gemma's 1 + w mode
+        # a MoE layer takes it where its decode kernels run (they fold the
+        # residual like the dense down projection), else the eager MLP tail
+        moe_kernels = (self.moe is not None and x.shape[0] <= 16
+                       and not torch.is_grad_enabled()
+                       and self.moe.decode_supported(h.dtype, h.device))
         add_norm = None
-        if self.moe is None and cfg.norm_type == "rms":
+        if self.moe is not None and not moe_kernels:
+            pass
+        elif cfg.norm_type == "rms":
             add_norm = C.add_rmsnorm_fwd
-        elif (self.moe is None and cfg.norm_type == "gemma_rms"
-              and ops.gemma_ops_enabled()):
+        elif cfg.norm_type == "gemma_rms" and ops.gemma_ops_enabled():
             add_norm = C.gemma_add_rmsnorm_fwd
         wo_bias = self.p.get(f"{i}.attn.wo.bias")
         o, kind = _decode_linear(
@@ -533,20 +539,26 @@ class ReaLModelBlock(nn.Module):
             # (x + o) + mlp-norm
             o = _norm(cfg, o, self.p[f"{i}.attn.post_ln.weight"], None)
         if add_norm is None:
-            return self._mlp(x + o, sp, fp8=fp8)
+            return self._mlp(x + o, sp, fp8=fp8, decode=True)
         h2, x2 = add_norm(o, x, self.p[f"{i}.mlp.ln.weight"],
                           cfg.layer_norm_epsilon)
+        if self.moe is not None:
+            if cfg.post_norms:
+                return x2 + _norm(cfg, self.moe.decode(h2),
+                                  self.p[f"{i}.mlp.post_ln.weight"], None)
+            return self.moe.decode(h2, residual=x2)
         if cfg.post_norms:
             # down without the residual fold: its output is normed first
             d = self._mlp_body(h2, sp, fp8=fp8)
             return x2 + _norm(cfg, d, self.p[f"{i}.mlp.post_ln.weight"], None)
         return self._mlp_body(h2, sp, residual=x2, fp8=fp8)
 
-    def _mlp(self, x, sp, fp8=None):
+    def _mlp(self, x, sp, fp8=None, decode=False):
         i = self.i
         h = _norm(self.cfg, x, self.p[f"{i}.mlp.ln.weight"], self.p.get(f"{i}.mlp.ln.bias"))
         if self.moe is not None:
-            d = self.moe(h)
+            # a decode step: the moe_decode kernels where their gate allows
+            d = self.moe.decode(h) if decode else self.moe(h)
         else:
             d = self._mlp_body(h, sp, fp8=fp8)  # residual not folded here
         if self.cfg.post_norms:

@@ -312,6 +312,51 @@ class MoELayer(torch.nn.Module):
             start += n
         return outs
 
+    # ------------------------------------------------------------- decode
+    def decode_stacks(self):
+        """(gate, up, down) expert stacks as the moe_decode kernels take
+        them (uniform stride, 16-byte aligned), or None.  Kept until the
+        weights move: walking E experts costs more than a decode step."""
+        i, last = self.i, self.local_e0 + self.n_local - 1
+        rw = self.router.weight
+        key = (self.p[f"{i}.mlp.experts.{self.local_e0}.gate.weight"].data_ptr(),
+               self.p[f"{i}.mlp.experts.{last}.down.weight"].data_ptr(),
+               rw.data_ptr())
+        if getattr(self, "_decode_stacks", (None,))[0] == key:
+            return self._decode_stacks[1]
+        stacks = tuple(self._expert_weight_stack(p)
+                       for p in ("gate", "up", "down"))
+        if rw.data_ptr() % 16 or not rw.is_contiguous() or any(
+                w is None or w.data_ptr() % 16 or w.stride(0) % 8
+                for w in stacks):
+            stacks = None
+        self._decode_stacks = (key, stacks)
+        return stacks
+
+    def decode_supported(self, dtype, device) -> bool:
+        """ops.moe_decode_supported for this layer, and its weights stack."""
+        from realhf_amd.ops import functional as ops
+
+        return (ops.moe_decode_supported(self.cfg, dtype, device,
+                                         self.tp_size, self.ep_size)
+                and self.decode_stacks() is not None)
+
+    def decode(self, h: torch.Tensor, residual=None) -> torch.Tensor:
+        """The layer for a decode step's rows (+ residual): the moe_decode
+        HIP kernels (no host sync, graph-capturable) where the gate allows
+        and there are at most 16 rows under no-grad, else forward."""
+        from realhf_amd.ops import functional as ops
+
+        if (not torch.is_grad_enabled()
+                and h.dim() == 2 and h.shape[0] <= ops.MOE_DECODE_MAX_ROWS
+                and self.decode_supported(h.dtype, h.device)):
+            moe = self.cfg.moe
+            return ops.moe_decode(
+                h.contiguous(), self.router.weight, *self.decode_stacks(),
+                moe.top_k, moe.norm_topk_prob, residual=residual)
+        d = self.forward(h)
+        return d if residual is None else residual + d
+
     # ------------------------------------------------------------ forward
     def forward(self, h: torch.Tensor) -> torch.Tensor:
         scores, idx, kept = self.router(h)  # [tokens, k]

@@ -133,6 +133,19 @@ torch::Tensor rope_qkv_decode_fp8_norm(
     torch::Tensor cache_seqlens, torch::Tensor cosb, torch::Tensor sinb,
     long nq, bool apply_rope, torch::Tensor q_w, torch::Tensor k_w,
     double eps);
+// MoE decode (M <= 16): router -> (idx [M, k] int32, wts [M, k] fp32); routed
+// gate/up + SwiGLU -> act [k, M, I]; routed down -> fp32 slabs [nks*k, M, H];
+// moe_combine sums the slabs in order (+ residual) -> bf16 [M, H]
+std::vector<torch::Tensor> moe_route_decode(torch::Tensor h,
+                                            torch::Tensor router_w, long top_k,
+                                            bool norm_topk);
+torch::Tensor moe_gate_up_swiglu(torch::Tensor h, torch::Tensor idx,
+                                 torch::Tensor wg, torch::Tensor wu,
+                                 c10::optional<torch::Tensor> out);
+torch::Tensor moe_down(torch::Tensor act, torch::Tensor idx, torch::Tensor wts,
+                       torch::Tensor wd, torch::Tensor out32_ws, long splitk);
+torch::Tensor moe_combine(torch::Tensor slabs, torch::Tensor like,
+                          c10::optional<torch::Tensor> residual);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -196,4 +209,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("qk_norm_rope_bwd", &qk_norm_rope_bwd);
   m.def("rope_qkv_decode_norm", &rope_qkv_decode_norm);
   m.def("rope_qkv_decode_fp8_norm", &rope_qkv_decode_fp8_norm);
+  m.def("moe_route_decode", &moe_route_decode);
+  m.def("moe_gate_up_swiglu", &moe_gate_up_swiglu, py::arg("h"),
+        py::arg("idx"), py::arg("wg"), py::arg("wu"),
+        py::arg("out") = py::none());
+  m.def("moe_down", &moe_down);
+  m.def("moe_combine", &moe_combine, py::arg("slabs"), py::arg("like"),
+        py::arg("residual") = py::none());
 }

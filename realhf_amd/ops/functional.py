@@ -37,6 +37,12 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        attn_decode over the pair (attn_decode_fp8);
                        REALHF_AMD_NO_FP8_KV=1 and the CPU take the
                        fp8_kv_*_ref / attn_decode_fp8_ref torch forms
+  moe_decode         — a MoE layer's MLP for M <= 16 decode rows: router
+                       (softmax + top-k), routed gate/up + SwiGLU, routed
+                       down and the slab combine (+ residual), no host sync;
+                       moe_decode_supported is its one gate, moe_decode_ref
+                       the CPU form (REALHF_AMD_NO_MOE_DECODE=1: the
+                       training route MoELayer.forward instead)
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -958,6 +964,119 @@ def _skinny_sem(device) -> torch.Tensor:
         t = torch.zeros(1024, dtype=torch.int32, device=device)
         _SKINNY_SEM[device] = t
     return t
+
+
+# ---------------------------------------------------------------------------
+# MoE decode: router + routed weight-streaming expert kernels (M <= 16)
+# ---------------------------------------------------------------------------
+MOE_DECODE_MAX_ROWS = 16
+MOE_DECODE_KSLICE = 1024  # the kernels' x stage, in K elements
+
+
+def moe_decode_enabled() -> bool:
+    """MoE decode steps run on the moe_decode kernels unless
+    REALHF_AMD_NO_MOE_DECODE=1 (read at call time), which keeps them on
+    MoELayer.forward: the A/B baseline and the model-level oracle of
+    tests/test_moe_decode_gpu.py."""
+    return os.environ.get("REALHF_AMD_NO_MOE_DECODE") != "1"
+
+
+def moe_decode_supported(cfg, dtype, device, tp: int = 1, ep: int = 1) -> bool:
+    """The one gate of the MoE decode kernels for a model: bf16 on the GPU,
+    no expert or tensor parallelism, no capacity limit, SwiGLU experts, an
+    inference router that is plain softmax + top-k, hidden and expert
+    intermediate sizes in multiples of 64, top_k <= 8 of <= 256 experts,
+    and the kill switch off.  (M <= 16, no-grad and the uniform weight
+    stack are run-time conditions: MoELayer.decode.)"""
+    moe = cfg.moe
+    return (
+        moe is not None
+        and moe_decode_enabled()
+        and torch.device(device).type == "cuda"
+        and dtype == torch.bfloat16
+        and tp == 1 and ep == 1
+        and moe.capacity_factor is None
+        and cfg.activation == "silu"
+        and not moe.input_jitter_eps
+        and moe.routing_type != "sinkhorn"
+        and cfg.hidden_dim % 64 == 0 and cfg.intermediate_dim % 64 == 0
+        and moe.top_k <= min(8, moe.num_experts) and moe.num_experts <= 256
+    )
+
+
+def moe_decode_ref(h, router_w, wg, wu, wd, top_k: int, norm_topk: bool,
+                   residual=None, routing=None):
+    """A MoE layer's MLP as a per-token loop in h's precision: fp32-or-wider
+    softmax over the router logits, top-k (renormalized if norm_topk), then
+    sum_j w_j * down_e(silu(gate_e(h_t)) * up_e(h_t)) over the token's
+    experts (+ residual).  wg / wu [E, I, H], wd [E, H, I].  The CPU form of
+    moe_decode and its test oracle; routing = (idx [M, k], weights [M, k])
+    takes the router's place."""
+    ct = torch.promote_types(h.dtype, torch.float32)
+    if routing is not None:
+        idx, scores = routing
+    else:
+        probs = torch.softmax(h.to(ct) @ router_w.to(ct).t(), dim=-1)
+        scores, idx = torch.topk(probs, top_k, dim=-1)
+        if norm_topk:
+            scores = scores / scores.sum(dim=-1, keepdim=True)
+    out = torch.zeros(h.shape[0], wd.shape[1], dtype=ct, device=h.device)
+    for t in range(h.shape[0]):
+        for j in range(idx.shape[1]):
+            e = int(idx[t, j])
+            a = (torch.nn.functional.silu((wg[e] @ h[t]).to(ct))
+                 * (wu[e] @ h[t]).to(ct)).to(h.dtype)
+            out[t] += scores[t, j] * (wd[e] @ a).to(ct)
+    if residual is not None:
+        out = out + residual.to(ct)
+    return out.to(h.dtype)
+
+
+def moe_down_splitk(idim: int) -> int:
+    """Split-K factor of moe_down: the fewest K slices that fit its x stage
+    (the expert and top-k dimensions already multiply the grid and the slab
+    count)."""
+    return -(-idim // MOE_DECODE_KSLICE)
+
+
+def moe_experts_decode(h, idx, wts, wg, wu, wd, residual=None, act=None,
+                       ws=None):
+    """The expert half of moe_decode for given routing: idx [M, k] int32
+    (distinct experts per row), wts [M, k] fp32.  act / ws: caller-owned
+    [k, M, I] bf16 and fp32 slab workspace (default: the global buffers)."""
+    from realhf_amd.base.constants import get_global_memory_buffer
+
+    C = _ops.require_hip()
+    k, hid, idim = idx.shape[1], wd.shape[1], wd.shape[2]
+    splitk = moe_down_splitk(idim)
+    if ws is None:
+        ws = get_global_memory_buffer().get_tensor(
+            (splitk * k * 16 * hid,), torch.float32, "moe_decode_ws")
+    if act is None:
+        # sized for 16 rows, like ws: its address does not depend on M
+        act = get_global_memory_buffer().get_tensor(
+            (k * 16 * idim,), torch.bfloat16, "moe_decode_act"
+        )[:k * h.shape[0] * idim]
+    act = C.moe_gate_up_swiglu(h, idx, wg, wu, act)
+    slabs = C.moe_down(act, idx, wts, wd, ws, splitk)
+    if residual is not None:
+        residual = residual.contiguous()
+    return C.moe_combine(slabs, h, residual)
+
+
+def moe_decode(h, router_w, wg, wu, wd, top_k: int, norm_topk: bool,
+               residual=None):
+    """A MoE layer's MLP (+ residual) for M <= 16 bf16 rows on the HIP
+    kernels: moe_route_decode, moe_gate_up_swiglu, moe_down and the slab
+    combine, four launches and no host sync.  wg / wu [E, I, H] and wd
+    [E, H, I] are expert stacks of contiguous rows (any expert stride).
+    Off the GPU: moe_decode_ref."""
+    if not _ops.use_hip(h):
+        return moe_decode_ref(h, router_w, wg, wu, wd, top_k, norm_topk,
+                              residual)
+    C = _ops.require_hip()
+    idx, wts = C.moe_route_decode(h, router_w, top_k, norm_topk)
+    return moe_experts_decode(h, idx, wts, wg, wu, wd, residual)
 
 
 # ---------------------------------------------------------------------------

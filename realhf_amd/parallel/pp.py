@@ -365,7 +365,11 @@ class PipelinedEngine(PipelinableEngine):
         use_graph = (
             gconfig.use_hip_graph
             and genmod.decode_graph_supported(cfg, dtype, dev)
-            and cfg.moe is None  # MoE counts.cpu() deadlocks under capture
+            # MoE counts.cpu() deadlocks under capture; the moe_decode
+            # kernels have no sync
+            and (cfg.moe is None
+                 or all(genmod.moe_decode_graph_supported(self.model, s.bs)
+                        for s in st))
         )
 
         last_rank = g.global_rank_of(S - 1, g.dp_rank, g.tp_rank)

@@ -24,6 +24,7 @@ SRC = [
     "realhf_amd/ops/csrc/qk_norm_rope.hip",
     "realhf_amd/ops/csrc/grouped_gemm.hip",
     "realhf_amd/ops/csrc/skinny_gemm.hip",
+    "realhf_amd/ops/csrc/moe_decode.hip",
     "realhf_amd/ops/csrc/attn_varlen.hip",
     "realhf_amd/ops/csrc/all_reduce.hip",
     "realhf_amd/ops/csrc/attn_bwd.hip",
