@@ -246,9 +246,17 @@ class Fp8DecodeWeights:
     the fp8 kernel does not take (N or K not a multiple of 64) has no pair
     and keeps its bf16 weight.  refresh() re-quantizes in place from the
     current flat_param views, so a captured graph keeps reading the same
-    addresses; installed() hands the pairs to the blocks for one generate()."""
+    addresses; installed() hands the pairs to the blocks for one generate().
 
-    def __init__(self, model: ReaLModel):
+    MoE blocks also get expert pairs, (q [E, N, K], scale [E, N]) for the
+    gate, up and down stacks (half the experts' bf16 bytes, on top of them),
+    when the decode batch `bs` is at most 16 rows and every MoE layer passes
+    fp8_decode_supported and REALHF_AMD_NO_FP8_MOE is not 1.  Otherwise all
+    experts stay bf16 (logged once per model): more than 16 rows decode on
+    MoELayer.forward with bf16 weights, and one generation must not mix the
+    two weight sets."""
+
+    def __init__(self, model: ReaLModel, bs: int = 1):
         self.blocks = [b for b in model.layers if isinstance(b, ReaLModelBlock)]
         self.pairs = []  # per block: key -> (q, scale)
         for blk in self.blocks:
@@ -262,26 +270,53 @@ class Fp8DecodeWeights:
                     torch.empty(n, dtype=torch.float32, device=w.device),
                 )
             self.pairs.append(d)
+        self.expert_pairs = []  # per block: () or the gate, up, down pairs
+        moes = [b.moe for b in self.blocks if b.moe is not None]
+        experts = (bool(moes) and ops.fp8_moe_enabled()
+                   and bs <= ops.MOE_DECODE_MAX_ROWS
+                   and all(m.fp8_decode_supported(model.dtype, model.device)
+                           for m in moes))
+        if moes and not experts and ops.fp8_moe_enabled() and not getattr(
+                model, "_fp8_moe_warned", False):
+            logger.warning(
+                "weight_quant=fp8_e4m3: MoE expert weights stay bf16 for this "
+                "model (decode batch %d > %d rows, or a MoE layer the "
+                "moe_decode kernels do not take)", bs, ops.MOE_DECODE_MAX_ROWS)
+            model._fp8_moe_warned = True
+        for blk in self.blocks:
+            self.expert_pairs.append(tuple(
+                (torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device),
+                 torch.empty(w.shape[:2], dtype=torch.float32, device=w.device))
+                for w in blk.moe.decode_stacks()
+            ) if experts and blk.moe is not None else ())
 
     def nbytes(self) -> int:
         return sum(q.numel() + 4 * s.numel()
-                   for d in self.pairs for q, s in d.values())
+                   for d, ep in zip(self.pairs, self.expert_pairs)
+                   for q, s in (*d.values(), *ep))
 
     def refresh(self):
-        for blk, d in zip(self.blocks, self.pairs):
+        for blk, d, ep in zip(self.blocks, self.pairs, self.expert_pairs):
             ws = blk.decode_weights()
             for key, pair in d.items():
                 ops.quantize_rows_e4m3(ws[key], out=pair)
+            if ep:  # one launch per stack
+                for w, pair in zip(blk.moe.decode_stacks(), ep):
+                    ops.quantize_rows_e4m3(w, out=pair)
 
     @contextlib.contextmanager
     def installed(self):
-        for blk, d in zip(self.blocks, self.pairs):
+        for blk, d, ep in zip(self.blocks, self.pairs, self.expert_pairs):
             blk.fp8 = d
+            if blk.moe is not None:
+                blk.moe.fp8 = ep
         try:
             yield self
         finally:
             for blk in self.blocks:
                 blk.fp8 = {}
+                if blk.moe is not None:
+                    blk.moe.fp8 = ()
 
 
 class GenerationSession:
@@ -316,6 +351,10 @@ def _session_key(model: ReaLModel, bs, cache_len, weight_quant: str,
         # likewise whether MoE layers decode on the moe_decode kernels or
         # (REALHF_AMD_NO_MOE_DECODE) on the training route, which no graph holds
         key += ("moe_decode", ops.moe_decode_enabled())
+        if weight_quant != "none":
+            # and whether the session holds e4m3 expert pairs
+            # (REALHF_AMD_NO_FP8_MOE: experts on the bf16 kernels)
+            key += ("fp8_moe", ops.fp8_moe_enabled())
     return key
 
 
@@ -345,7 +384,7 @@ def _get_session(model: ReaLModel, bs, cache_len, nkv_local, device,
             )
             for _ in range(n_blocks)
         ]
-    fp8 = Fp8DecodeWeights(model) if weight_quant == "fp8_e4m3" else None
+    fp8 = Fp8DecodeWeights(model, bs) if weight_quant == "fp8_e4m3" else None
     s = GenerationSession(kv_caches, DecodeGraph(model, kv_caches, bs), fp8)
     model._gen_session = (key, s)
     return s

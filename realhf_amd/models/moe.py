@@ -228,6 +228,10 @@ class MoELayer(torch.nn.Module):
         assert self.n_experts % ep_size == 0
         self.n_local = self.n_experts // ep_size
         self.local_e0 = ep_rank * self.n_local
+        # FP8 weight-only decode: () or the (q [E, N, K], scale [E, N])
+        # pairs of the gate, up and down stacks, installed by the generation
+        # session for the span of one generate() and read by decode() only
+        self.fp8: tuple = ()
 
     # ---------------------------------------------------------------- mlp
     def _expert_ffn(self, e_local: int, x: torch.Tensor) -> torch.Tensor:
@@ -341,19 +345,36 @@ class MoELayer(torch.nn.Module):
                                          self.tp_size, self.ep_size)
                 and self.decode_stacks() is not None)
 
+    def fp8_decode_supported(self, dtype, device) -> bool:
+        """May this layer decode from e4m3 expert pairs?  On the GPU where
+        the moe_decode kernels run it (decode_supported); off the GPU, where
+        ops.moe_decode is moe_decode_ref on the dequantised stacks in any
+        precision, under the same conditions but the device and dtype."""
+        from realhf_amd.ops import functional as ops
+
+        if torch.device(device).type == "cuda":
+            return self.decode_supported(dtype, device)
+        return (ops.moe_decode_supported(self.cfg, torch.bfloat16, "cuda",
+                                         self.tp_size, self.ep_size)
+                and self.decode_stacks() is not None)
+
     def decode(self, h: torch.Tensor, residual=None) -> torch.Tensor:
         """The layer for a decode step's rows (+ residual): the moe_decode
         HIP kernels (no host sync, graph-capturable) where the gate allows
-        and there are at most 16 rows under no-grad, else forward."""
+        and there are at most 16 rows under no-grad, else forward.  With
+        expert pairs installed (self.fp8) the experts are the quantized
+        ones: the FP8 kernels, or off the GPU their reference form."""
         from realhf_amd.ops import functional as ops
 
         if (not torch.is_grad_enabled()
                 and h.dim() == 2 and h.shape[0] <= ops.MOE_DECODE_MAX_ROWS
-                and self.decode_supported(h.dtype, h.device)):
+                and (self.decode_supported(h.dtype, h.device)
+                     or (self.fp8 and not h.is_cuda))):
             moe = self.cfg.moe
             return ops.moe_decode(
                 h.contiguous(), self.router.weight, *self.decode_stacks(),
-                moe.top_k, moe.norm_topk_prob, residual=residual)
+                moe.top_k, moe.norm_topk_prob, residual=residual,
+                fp8=self.fp8 or None)
         d = self.forward(h)
         return d if residual is None else residual + d
 

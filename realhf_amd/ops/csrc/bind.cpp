@@ -146,6 +146,16 @@ torch::Tensor moe_down(torch::Tensor act, torch::Tensor idx, torch::Tensor wts,
                        torch::Tensor wd, torch::Tensor out32_ws, long splitk);
 torch::Tensor moe_combine(torch::Tensor slabs, torch::Tensor like,
                           c10::optional<torch::Tensor> residual);
+// the same over FP8 expert stacks: e4m3 codes q [E, N, K] (expert stride a
+// multiple of 16 bytes) and fp32 row scales [E, N] from quantize_rows_e4m3
+torch::Tensor moe_gate_up_swiglu_fp8(torch::Tensor h, torch::Tensor idx,
+                                     torch::Tensor qg, torch::Tensor sg,
+                                     torch::Tensor qu, torch::Tensor su,
+                                     c10::optional<torch::Tensor> out);
+torch::Tensor moe_down_fp8(torch::Tensor act, torch::Tensor idx,
+                           torch::Tensor wts, torch::Tensor qd,
+                           torch::Tensor sd, torch::Tensor out32_ws,
+                           long splitk);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -214,6 +224,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("idx"), py::arg("wg"), py::arg("wu"),
         py::arg("out") = py::none());
   m.def("moe_down", &moe_down);
+  m.def("moe_gate_up_swiglu_fp8", &moe_gate_up_swiglu_fp8, py::arg("h"),
+        py::arg("idx"), py::arg("qg"), py::arg("sg"), py::arg("qu"),
+        py::arg("su"), py::arg("out") = py::none());
+  m.def("moe_down_fp8", &moe_down_fp8);
   m.def("moe_combine", &moe_combine, py::arg("slabs"), py::arg("like"),
         py::arg("residual") = py::none());
 }

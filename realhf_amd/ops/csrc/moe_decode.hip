@@ -12,7 +12,9 @@
 //                       grid (H/64, E, nks)
 //
 // and sg_combine_slabs (skinny_gemm.h) sums the nks*k slabs in order, folds the
-// residual and rounds to bf16 once: the layer output.
+// residual and rounds to bf16 once: the layer output.  moe_gate_up_swiglu_fp8
+// and moe_down_fp8 (section 4) are the two expert kernels over e4m3 codes with
+// per-row scales.
 //
 // Routing inside the expert kernels.  A workgroup belongs to one expert e.
 // Lanes 0..15 of every wave scan idx (<= 128 ints): lane t finds the slot j
@@ -57,9 +59,14 @@ DEVINL int moe_slot(const int* __restrict__ idx, int M, int k, int e, int lane) 
   return slot;
 }
 
-// this lane's view of NS weight rows and of x_s (bf16: 32 k per 16-byte load)
-template <int NS>
+// this lane's view of NS weight rows and of x_s.  KB = k elements per 16-byte
+// W load: 32 (bf16) or 64 (FP8: e4m3 codes, SgLane<true>'s fragment mapping:
+// the lane owns k in [16g, 16g + 16) of each 64-block, its low 8 bytes feed
+// the first MFMA of the load and its high 8 bytes the second)
+template <int NS, bool FP8 = false>
 struct MoeLane {
+  static constexpr int KB = FP8 ? 64 : 32;
+  static constexpr int WB = FP8 ? 1 : 2;  // bytes per W element
   const char* wl[NS];  // the lane's W bytes for k = 0, per stream
   const __bf16* x_s;
   int xo;              // x_s index of the lane's first element of k is xo + k
@@ -67,99 +74,117 @@ struct MoeLane {
 
 // full = false: NB loads of the block at k (a slice shorter than a batch must
 // not be read past its end)
-template <int NS, int NB>
-DEVINL void moe_ldw(int4v (&b)[NS][NB], const MoeLane<NS>& ln, int k,
+template <int NS, int NB, bool FP8>
+DEVINL void moe_ldw(int4v (&b)[NS][NB], const MoeLane<NS, FP8>& ln, int k,
                     bool full = true) {
+  constexpr int KB = MoeLane<NS, FP8>::KB, WB = MoeLane<NS, FP8>::WB;
   #pragma unroll
   for (int s = 0; s < NS; s++) {
     #pragma unroll
     for (int t = 0; t < NB; t++)
-      b[s][t] = *(const int4v*)(ln.wl[s] + (long)(full ? k + t * 32 : k) * 2);
+      b[s][t] = *(const int4v*)(ln.wl[s] + (long)(full ? k + t * KB : k) * WB);
   }
   __builtin_amdgcn_sched_barrier(0);  // issued HERE, as SgLane::ldw_batch
 }
 
 // one A fragment per k block, shared by the streams; element t on acc[.][j & 3]
-template <int NS>
-DEVINL void moe_mma1(f32x4 (&acc)[NS][4], const MoeLane<NS>& ln,
+// (FP8: two A fragments and two MFMAs per load, on acc[.][2j & 3] and
+// acc[.][(2j + 1) & 3]; the codes reach the MFMA exactly, the row scale waits
+// for the epilogue)
+template <int NS, bool FP8>
+DEVINL void moe_mma1(f32x4 (&acc)[NS][4], const MoeLane<NS, FP8>& ln,
                      const int4v (&b)[NS], int k, int j) {
   const bf16x8 a = *(const bf16x8*)(&ln.x_s[ln.xo + k]);
-  #pragma unroll
-  for (int s = 0; s < NS; s++)
-    acc[s][j & 3] = mfma16(a, __builtin_bit_cast(bf16x8, b[s]), acc[s][j & 3]);
+  if constexpr (FP8) {
+    const bf16x8 a1 = *(const bf16x8*)(&ln.x_s[ln.xo + k + 8]);
+    #pragma unroll
+    for (int s = 0; s < NS; s++) {
+      acc[s][(2 * j) & 3] = mfma16(a, sg_e4m3x8_to_bf16(b[s][0], b[s][1]),
+                                   acc[s][(2 * j) & 3]);
+      acc[s][(2 * j + 1) & 3] = mfma16(a1, sg_e4m3x8_to_bf16(b[s][2], b[s][3]),
+                                       acc[s][(2 * j + 1) & 3]);
+    }
+  } else {
+    #pragma unroll
+    for (int s = 0; s < NS; s++)
+      acc[s][j & 3] = mfma16(a, __builtin_bit_cast(bf16x8, b[s]), acc[s][j & 3]);
+  }
 }
 
-template <int NS, int NB>
-DEVINL void moe_mma(f32x4 (&acc)[NS][4], const MoeLane<NS>& ln,
+template <int NS, int NB, bool FP8>
+DEVINL void moe_mma(f32x4 (&acc)[NS][4], const MoeLane<NS, FP8>& ln,
                     const int4v (&b)[NS][NB], int k) {
   #pragma unroll
   for (int t = 0; t < NB; t++) {
     int4v bt[NS];
     #pragma unroll
     for (int s = 0; s < NS; s++) bt[s] = b[s][t];
-    moe_mma1<NS>(acc, ln, bt, k + t * 32, t);
+    moe_mma1<NS, FP8>(acc, ln, bt, k + t * MoeLane<NS, FP8>::KB, t);
   }
 }
 
 // the end of a slice (sg_finish for NS streams): the NTL tail loads of every
 // stream go out together, then the MFMAs of the last full batch, then the
-// tail's (on acc[.][0])
-template <int NS, int NB, int NTL>
-DEVINL void moe_finish(f32x4 (&acc)[NS][4], const MoeLane<NS>& ln,
+// tail's (on acc[.][0]; FP8: acc[.][0] and acc[.][1])
+template <int NS, int NB, int NTL, bool FP8>
+DEVINL void moe_finish(f32x4 (&acc)[NS][4], const MoeLane<NS, FP8>& ln,
                        const int4v (&last)[NS][NB], bool has_last, int k) {
-  const int kt = has_last ? k + NB * 32 : k;
+  constexpr int KB = MoeLane<NS, FP8>::KB, WB = MoeLane<NS, FP8>::WB;
+  const int kt = has_last ? k + NB * KB : k;
   int4v tb[NTL > 0 ? NTL : 1][NS];
   #pragma unroll
   for (int t = 0; t < NTL; t++) {
     #pragma unroll
     for (int s = 0; s < NS; s++)
-      tb[t][s] = *(const int4v*)(ln.wl[s] + (long)(kt + t * 32) * 2);
+      tb[t][s] = *(const int4v*)(ln.wl[s] + (long)(kt + t * KB) * WB);
   }
   __builtin_amdgcn_sched_barrier(0);
-  if (has_last) moe_mma<NS, NB>(acc, ln, last, k);
+  if (has_last) moe_mma<NS, NB, FP8>(acc, ln, last, k);
   #pragma unroll
-  for (int t = 0; t < NTL; t++) moe_mma1<NS>(acc, ln, tb[t], kt + t * 32, 0);
+  for (int t = 0; t < NTL; t++)
+    moe_mma1<NS, FP8>(acc, ln, tb[t], kt + t * KB, 0);
 }
 
-template <int NS, int NB, int NTL = 0>
-DEVINL void moe_finish_n(f32x4 (&acc)[NS][4], const MoeLane<NS>& ln,
+template <int NS, int NB, bool FP8, int NTL = 0>
+DEVINL void moe_finish_n(f32x4 (&acc)[NS][4], const MoeLane<NS, FP8>& ln,
                          const int4v (&last)[NS][NB], bool has_last, int k,
                          int ntail) {
-  if (ntail == NTL) moe_finish<NS, NB, NTL>(acc, ln, last, has_last, k);
+  if (ntail == NTL) moe_finish<NS, NB, NTL, FP8>(acc, ln, last, has_last, k);
   else if constexpr (NTL + 2 < NB)
-    moe_finish_n<NS, NB, NTL + 1>(acc, ln, last, has_last, k, ntail);
-  else moe_finish<NS, NB, NB - 1>(acc, ln, last, has_last, k);
+    moe_finish_n<NS, NB, FP8, NTL + 1>(acc, ln, last, has_last, k, ntail);
+  else moe_finish<NS, NB, NB - 1, FP8>(acc, ln, last, has_last, k);
 }
 
 // the W stream of one slice [k_lo, k_hi) once x_s holds it: b0 carries (in
 // flight) the first batch, issued by the caller before it stored x.  Same
 // issue order and MFMA order as sg_slice.
-template <int NS, int NB>
-DEVINL void moe_stream(f32x4 (&acc)[NS][4], const MoeLane<NS>& ln,
+template <int NS, int NB, bool FP8>
+DEVINL void moe_stream(f32x4 (&acc)[NS][4], const MoeLane<NS, FP8>& ln,
                        int4v (&b0)[NS][NB], int k_lo, int k_hi) {
-  constexpr int S = NB * 32;
+  constexpr int KB = MoeLane<NS, FP8>::KB;
+  constexpr int S = NB * KB;
   int nb = (k_hi - k_lo) / S;
-  const int ntail = ((k_hi - k_lo) - nb * S) / 32;
+  const int ntail = ((k_hi - k_lo) - nb * S) / KB;
   int kk = k_lo;
   if (nb == 0) {
-    moe_finish_n<NS, NB>(acc, ln, b0, false, kk, ntail);
+    moe_finish_n<NS, NB, FP8>(acc, ln, b0, false, kk, ntail);
     return;
   }
   int4v b1[NS][NB];
   while (nb > 2) {
-    moe_ldw<NS, NB>(b1, ln, kk + S);
-    moe_mma<NS, NB>(acc, ln, b0, kk);
-    moe_ldw<NS, NB>(b0, ln, kk + 2 * S);
-    moe_mma<NS, NB>(acc, ln, b1, kk + S);
+    moe_ldw<NS, NB, FP8>(b1, ln, kk + S);
+    moe_mma<NS, NB, FP8>(acc, ln, b0, kk);
+    moe_ldw<NS, NB, FP8>(b0, ln, kk + 2 * S);
+    moe_mma<NS, NB, FP8>(acc, ln, b1, kk + S);
     kk += 2 * S;
     nb -= 2;
   }
   if (nb == 2) {
-    moe_ldw<NS, NB>(b1, ln, kk + S);
-    moe_mma<NS, NB>(acc, ln, b0, kk);
-    moe_finish_n<NS, NB>(acc, ln, b1, true, kk + S, ntail);
+    moe_ldw<NS, NB, FP8>(b1, ln, kk + S);
+    moe_mma<NS, NB, FP8>(acc, ln, b0, kk);
+    moe_finish_n<NS, NB, FP8>(acc, ln, b1, true, kk + S, ntail);
   } else {
-    moe_finish_n<NS, NB>(acc, ln, b0, true, kk, ntail);
+    moe_finish_n<NS, NB, FP8>(acc, ln, b0, true, kk, ntail);
   }
 }
 
@@ -308,11 +333,11 @@ __global__ __launch_bounds__(MOE_NT, 2) void moe_gate_up_kernel(
     int4v b0[2][NB];
     // unconditional, as in sg_slice: the first block again when the slice
     // has no full batch (those registers are then not used)
-    moe_ldw<2, NB>(b0, ln, k_lo, k_hi - k_lo >= NB * 32);
+    moe_ldw<2, NB, false>(b0, ln, k_lo, k_hi - k_lo >= NB * 32);
     if (k_lo > 0) __syncthreads();  // every wave is done with the last stage
     sg_x_store<MOE_NT>(x_s, xv, h, M, H, k_lo, k_hi, kslice);
     __syncthreads();
-    moe_stream<2, NB>(acc, ln, b0, k_lo, k_hi);
+    moe_stream<2, NB, false>(acc, ln, b0, k_lo, k_hi);
   }
 
   #pragma unroll
@@ -390,7 +415,7 @@ __global__ __launch_bounds__(MOE_NT, 4) void moe_down_kernel(
   bf16x8 xv[SG_XV];
   moe_x_gather<MOE_NT>(xv, act, slot, M, I, k_lo, k_hi, kslice);
   int4v b0[1][NB];
-  moe_ldw<1, NB>(b0, ln, k_lo, k_hi - k_lo >= NB * 32);
+  moe_ldw<1, NB, false>(b0, ln, k_lo, k_hi - k_lo >= NB * 32);
   #pragma unroll
   for (int t = 0; t < SG_XV; t++) {  // kslice <= NT * SG_XV / 2: no remainder
     const int i = (threadIdx.x + t * MOE_NT) * 8;
@@ -398,7 +423,7 @@ __global__ __launch_bounds__(MOE_NT, 4) void moe_down_kernel(
   }
   __syncthreads();
   f32x4 acc[1][4] = {};
-  moe_stream<1, NB>(acc, ln, b0, k_lo, k_hi);
+  moe_stream<1, NB, false>(acc, ln, b0, k_lo, k_hi);
 
   #pragma unroll
   for (int r = 0; r < 4; r++) {
@@ -406,6 +431,156 @@ __global__ __launch_bounds__(MOE_NT, 4) void moe_down_kernel(
     const float vsum = acc[0][0][r] + acc[0][1][r] + acc[0][2][r] + acc[0][3][r];
     if (js[r] >= 0)  // slab (ks, slot) row m
       out32[(((long)ks * k + js[r]) * M + m) * H + n0 + i16] = vsum * rw[r];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// 4. FP8 (e4m3) expert weights.  The stacks are codes q [E, N, K], one byte
+// per element, with one fp32 scale per row, scale [E, N] (quantize_fp8.hip).
+// Routing, x stage, slabs and the one-writer rule are the bf16 kernels'; the
+// lanes stream 16 codes per load (MoeLane<NS, true>) and the row scale
+// multiplies the fp32 sum once, in the epilogue: gate and up before SwiGLU,
+// down together with the routing weight.  The scale loads go out before the
+// stream, after the idle-expert return: an idle expert's codes and scales are
+// never read.
+//
+// Load plan of gate/up.  A 1024-element x stage now holds 16 loads per lane
+// and stream instead of 32, so the slice boundary of the bf16 kernel
+// (barrier, x load, x store, barrier, with the W pipeline drained) weighs
+// twice as much per byte.  This kernel double-buffers two 1024 stages (64
+// KiB, two workgroups per CU still fit): a full slice is MOE_KSLICE /
+// (NB * 64) batches, and before the MFMAs of its last batch the next slice's
+// x loads and first W batch are issued; x is stored to the other stage behind
+// those MFMAs and ONE barrier follows (the other stage was last read in the
+// previous slice, which every wave left through that slice's barrier).  The
+// W stream never drains between slices.  The last slice (any length) is
+// moe_stream.  Measured against the bf16 kernel's loop over codes and against
+// one 2048 stage: docs/kernels.md "MoE decode, FP8 experts".
+// ---------------------------------------------------------------------------
+template <int NB>
+__global__ __launch_bounds__(MOE_NT, 2) void moe_gate_up_fp8_kernel(
+    const bf16* __restrict__ h, const int* __restrict__ idx,
+    const unsigned char* __restrict__ qg, const float* __restrict__ sg,
+    const unsigned char* __restrict__ qu, const float* __restrict__ su,
+    bf16* __restrict__ act, int M, int H, int I, int k, long estride_g,
+    long estride_u, int kslice) {
+  const int e = blockIdx.y;
+  const auto [lane, wv, i16, g] = mfma_lane();
+  const int slot = moe_slot(idx, M, k, e, lane);
+  if (__ballot(slot >= 0) == 0) return;  // idle expert: no weight load issued
+
+  extern __shared__ __bf16 x_s[];  // [16][kslice], twice when H > kslice
+  const int n0 = blockIdx.x * SG_TN + wv * 16;
+  const float scg = sg[(long)e * I + n0 + i16];  // first out
+  const float scu = su[(long)e * I + n0 + i16];
+  MoeLane<2, true> ln;
+  ln.wl[0] = (const char*)(qg + e * estride_g + (long)(n0 + i16) * H) + g * 16;
+  ln.wl[1] = (const char*)(qu + e * estride_u + (long)(n0 + i16) * H) + g * 16;
+  ln.x_s = x_s;
+
+  constexpr int S = NB * 64;
+  f32x4 acc[2][4] = {};
+  // kslice == MOE_KSLICE whenever a second slice exists (host side)
+  static_assert(MOE_KSLICE % (2 * S) == 0, "a full slice is batch pairs");
+  bf16x8 xv[SG_XV];
+  int4v b0[2][NB], b1[2][NB];
+  sg_x_load<MOE_NT>(xv, h, M, H, 0, min(H, kslice), kslice);
+  moe_ldw<2, NB, true>(b0, ln, 0, min(H, kslice) >= S);
+  sg_x_store<MOE_NT>(x_s, xv, h, M, H, 0, min(H, kslice), kslice);
+  __syncthreads();
+  int st = 0;
+  int k_lo = 0;
+  for (; k_lo + kslice < H; k_lo += kslice, st ^= 1) {  // full, not the last
+    ln.x_s = x_s + st * 16 * kslice;
+    ln.xo = i16 * kslice + g * 16 - k_lo;
+    const int n_lo = k_lo + kslice, n_hi = min(H, n_lo + kslice);
+    #pragma unroll
+    for (int kk = 0; kk < MOE_KSLICE; kk += 2 * S) {
+      moe_ldw<2, NB, true>(b1, ln, k_lo + kk + S);
+      moe_mma<2, NB, true>(acc, ln, b0, k_lo + kk);
+      if (kk + 2 * S < MOE_KSLICE) {
+        moe_ldw<2, NB, true>(b0, ln, k_lo + kk + 2 * S);
+      } else {  // the next slice's x and first batch, behind b1's loads
+        sg_x_load<MOE_NT>(xv, h, M, H, n_lo, n_hi, kslice);
+        moe_ldw<2, NB, true>(b0, ln, n_lo, n_hi - n_lo >= S);
+      }
+      moe_mma<2, NB, true>(acc, ln, b1, k_lo + kk + S);
+    }
+    sg_x_store<MOE_NT>(x_s + (st ^ 1) * 16 * kslice, xv, h, M, H, n_lo, n_hi,
+                       kslice);
+    __syncthreads();
+  }
+  ln.x_s = x_s + st * 16 * kslice;
+  ln.xo = i16 * kslice + g * 16 - k_lo;
+  moe_stream<2, NB, true>(acc, ln, b0, k_lo, H);
+
+  #pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int m = g * 4 + r;
+    const int j = __shfl(slot, m, 64);
+    const float gs =
+        (acc[0][0][r] + acc[0][1][r] + acc[0][2][r] + acc[0][3][r]) * scg;
+    const float us =
+        (acc[1][0][r] + acc[1][1][r] + acc[1][2][r] + acc[1][3][r]) * scu;
+    const float a = gs / (1.f + __expf(-gs)) * us;
+    if (j >= 0)  // j >= 0 implies m < M
+      ((short*)act)[((long)j * M + m) * I + n0 + i16] = f2bf(a);
+  }
+}
+
+// the bf16 down kernel over codes: gathered x stage, one K-slice per workgroup
+template <int NB>
+__global__ __launch_bounds__(MOE_NT, 4) void moe_down_fp8_kernel(
+    const bf16* __restrict__ act, const int* __restrict__ idx,
+    const float* __restrict__ wts, const unsigned char* __restrict__ qd,
+    const float* __restrict__ sd, float* __restrict__ out32, int M, int H,
+    int I, int k, long estride, int kslice) {
+  const int e = blockIdx.y;
+  const int ks = blockIdx.z;
+  const auto [lane, wv, i16, g] = mfma_lane();
+  const int slot = moe_slot(idx, M, k, e, lane);
+  if (__ballot(slot >= 0) == 0) return;  // idle expert: no weight load issued
+
+  extern __shared__ __bf16 x_s[];  // [16][kslice], kslice <= MOE_KSLICE
+  const int k_lo = ks * kslice;
+  const int k_hi = min(I, k_lo + kslice);
+  const int n0 = blockIdx.x * SG_TN + wv * 16;
+  const float sc = sd[(long)e * H + n0 + i16];  // first out
+  MoeLane<1, true> ln;
+  ln.wl[0] = (const char*)(qd + e * estride + (long)(n0 + i16) * I) + g * 16;
+  ln.x_s = x_s;
+  ln.xo = i16 * kslice + g * 16 - k_lo;
+
+  // the lane's four output rows: slot and routing weight
+  int js[4];
+  float rw[4];
+  #pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int m = g * 4 + r;
+    js[r] = __shfl(slot, m, 64);
+    rw[r] = wts[js[r] >= 0 ? m * k + js[r] : 0];
+  }
+
+  bf16x8 xv[SG_XV];
+  moe_x_gather<MOE_NT>(xv, act, slot, M, I, k_lo, k_hi, kslice);
+  int4v b0[1][NB];
+  moe_ldw<1, NB, true>(b0, ln, k_lo, k_hi - k_lo >= NB * 64);
+  #pragma unroll
+  for (int t = 0; t < SG_XV; t++) {  // kslice <= NT * SG_XV / 2: no remainder
+    const int i = (threadIdx.x + t * MOE_NT) * 8;
+    if (i < 16 * kslice) *(bf16x8*)(&x_s[i]) = xv[t];
+  }
+  __syncthreads();
+  f32x4 acc[1][4] = {};
+  moe_stream<1, NB, true>(acc, ln, b0, k_lo, k_hi);
+
+  #pragma unroll
+  for (int r = 0; r < 4; r++) {
+    const int m = g * 4 + r;
+    const float vsum = acc[0][0][r] + acc[0][1][r] + acc[0][2][r] + acc[0][3][r];
+    if (js[r] >= 0)  // slab (ks, slot) row m
+      out32[(((long)ks * k + js[r]) * M + m) * H + n0 + i16] =
+          vsum * sc * rw[r];
   }
 }
 
@@ -526,6 +701,91 @@ torch::Tensor moe_down(torch::Tensor act, torch::Tensor idx, torch::Tensor wts,
     (const bf16*)act.data_ptr(), idx.data_ptr<int>(), wts.data_ptr<float>(),
     (const bf16*)wd.data_ptr(), out32_ws.data_ptr<float>(), (int)M, (int)H,
     (int)I, (int)k, sd, kslice);
+  CHECK_CUDA_OK();
+  return out32_ws.flatten().narrow(0, 0, (long)nks * k * M * H)
+      .view({(long)nks * k, M, H});
+}
+
+// q [E, N, K] e4m3 codes (one byte per element), rows contiguous, any expert
+// stride that is a multiple of 16; scale fp32 [E, N] contiguous.  Returns the
+// expert stride in bytes.
+static long moe_check_stack_fp8(const torch::Tensor& q,
+                                const torch::Tensor& scale, long E, long N,
+                                long K, const char* what) {
+  TORCH_CHECK(q.is_cuda() && q.element_size() == 1 && q.dim() == 3 &&
+              q.size(0) == E && q.size(1) == N && q.size(2) == K &&
+              q.stride(2) == 1 && q.stride(1) == K && q.stride(0) % 16 == 0 &&
+              q.stride(0) >= N * K && (uintptr_t)q.data_ptr() % 16 == 0 &&
+              N % SG_TN == 0 && K % 64 == 0,
+              what, " codes must be a 16-byte aligned one-byte [E, N % 64 == 0, "
+              "K % 64 == 0] stack of contiguous rows, expert stride % 16 == 0");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat32 &&
+              scale.dim() == 2 && scale.is_contiguous() &&
+              scale.size(0) == E && scale.size(1) == N,
+              what, " scale must be contiguous fp32 [E, N]");
+  return q.stride(0);
+}
+
+torch::Tensor moe_gate_up_swiglu_fp8(torch::Tensor h, torch::Tensor idx,
+                                     torch::Tensor qg, torch::Tensor sg,
+                                     torch::Tensor qu, torch::Tensor su,
+                                     c10::optional<torch::Tensor> out) {
+  moe_check_rows(h, "h");
+  const long M = h.size(0), H = h.size(1);
+  moe_check_idx(idx, M);
+  TORCH_CHECK(qg.dim() == 3, "qg must be [E, I, H]");
+  const long k = idx.size(1), E = qg.size(0), I = qg.size(1);
+  const long eg = moe_check_stack_fp8(qg, sg, E, I, H, "gate");
+  const long eu = moe_check_stack_fp8(qu, su, E, I, H, "up");
+  TORCH_CHECK(E <= MOE_MAX_E, "at most 256 experts");
+  auto act = out.has_value() ? *out : torch::empty({k, M, I}, h.options());
+  TORCH_CHECK(act.is_cuda() && act.scalar_type() == torch::kBFloat16 &&
+              act.is_contiguous() && act.numel() == k * M * I,
+              "out must be contiguous bf16 [k, M, I]");
+  const int kslice = (int)std::min<long>(H, MOE_KSLICE);
+  const int stages = H > kslice ? 2 : 1;  // double-buffered past one slice
+  hipLaunchKernelGGL((moe_gate_up_fp8_kernel<4>), dim3(I / SG_TN, E),
+    dim3(MOE_NT), (size_t)stages * 16 * kslice * sizeof(short), cur_stream(),
+    (const bf16*)h.data_ptr(), idx.data_ptr<int>(),
+    (const unsigned char*)qg.data_ptr(), sg.data_ptr<float>(),
+    (const unsigned char*)qu.data_ptr(), su.data_ptr<float>(),
+    (bf16*)act.data_ptr(), (int)M, (int)H, (int)I, (int)k, eg, eu, kslice);
+  CHECK_CUDA_OK();
+  return act.view({k, M, I});
+}
+
+torch::Tensor moe_down_fp8(torch::Tensor act, torch::Tensor idx,
+                           torch::Tensor wts, torch::Tensor qd,
+                           torch::Tensor sd, torch::Tensor out32_ws,
+                           long splitk) {
+  TORCH_CHECK(act.is_cuda() && act.scalar_type() == torch::kBFloat16 &&
+              act.dim() == 3 && act.is_contiguous() &&
+              (uintptr_t)act.data_ptr() % 16 == 0 && act.size(1) >= 1 &&
+              act.size(1) <= 16,
+              "act must be contiguous, 16-byte aligned bf16 [k, M <= 16, I]");
+  const long k = act.size(0), M = act.size(1), I = act.size(2);
+  moe_check_idx(idx, M);
+  TORCH_CHECK(idx.size(1) == k, "act / idx top-k mismatch");
+  TORCH_CHECK(wts.is_cuda() && wts.scalar_type() == torch::kFloat32 &&
+              wts.is_contiguous() && wts.dim() == 2 && wts.size(0) == M &&
+              wts.size(1) == k, "wts must be contiguous fp32 [M, k]");
+  TORCH_CHECK(qd.dim() == 3, "qd must be [E, H, I]");
+  const long E = qd.size(0), H = qd.size(1);
+  const long ed = moe_check_stack_fp8(qd, sd, E, H, I, "down");
+  TORCH_CHECK(E <= MOE_MAX_E, "at most 256 experts");
+  TORCH_CHECK(splitk >= 1);
+  const int kslice = (int)((I / splitk + 63) / 64 * 64);
+  const int nks = (int)((I + kslice - 1) / kslice);
+  TORCH_CHECK(kslice <= MOE_KSLICE, "splitk too small: a K slice of ", kslice,
+              " exceeds the ", MOE_KSLICE, "-element x stage");
+  TORCH_CHECK(out32_ws.is_cuda() && out32_ws.scalar_type() == torch::kFloat32 &&
+              out32_ws.is_contiguous() &&
+              out32_ws.numel() >= (long)nks * k * M * H, "workspace too small");
+  hipLaunchKernelGGL((moe_down_fp8_kernel<4>), dim3(H / SG_TN, E, nks),
+    dim3(MOE_NT), (size_t)16 * kslice * sizeof(short), cur_stream(),
+    (const bf16*)act.data_ptr(), idx.data_ptr<int>(), wts.data_ptr<float>(),
+    (const unsigned char*)qd.data_ptr(), sd.data_ptr<float>(),
+    out32_ws.data_ptr<float>(), (int)M, (int)H, (int)I, (int)k, ed, kslice);
   CHECK_CUDA_OK();
   return out32_ws.flatten().narrow(0, 0, (long)nks * k * M * H)
       .view({(long)nks * k, M, H});

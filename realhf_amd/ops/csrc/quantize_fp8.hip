@@ -6,7 +6,8 @@
 // The scale, the correctly rounded division, the clamp and the conversion
 // are fp8_e4m3.h's, shared with the FP8 KV cache writers: the result is bit
 // for bit what quantize_rows_e4m3_ref computes on the CPU.  Rows with
-// non-finite weights get no special handling.
+// non-finite weights get no special handling.  An expert stack w [E, N, K]
+// (uniform expert stride) is quantized in one launch, slice by slice the same.
 //
 // Shape follows rmsnorm.hip: one 256-thread workgroup per row, 16-byte
 // loads, the row read twice (amax pass, quantize pass; the second read hits
@@ -18,14 +19,12 @@
 
 // VEC = 8: 16-byte loads, 8-byte stores; VEC = 1: rows that are not
 // 16-byte aligned or K % 8 != 0
+// one row: wr its K bf16 values, qr its K codes, row = its index in scale
 template <int VEC>
-__global__ __launch_bounds__(QF8_THREADS) void quantize_rows_e4m3_kernel(
-    const bf16* __restrict__ w, long wstride, unsigned char* __restrict__ q,
-    float* __restrict__ scale, int K) {
+DEVINL void quantize_row_e4m3(const short* __restrict__ wr,
+                              unsigned char* __restrict__ qr,
+                              float* __restrict__ scale, long row, int K) {
   __shared__ float red[QF8_THREADS / WAVE];
-  const long row = blockIdx.x;
-  const short* wr = (const short*)w + row * wstride;
-  unsigned char* qr = q + row * K;
 
   float amax = 0.f;
   for (int i = threadIdx.x * VEC; i < K; i += QF8_THREADS * VEC) {
@@ -61,9 +60,64 @@ __global__ __launch_bounds__(QF8_THREADS) void quantize_rows_e4m3_kernel(
   }
 }
 
+template <int VEC>
+__global__ __launch_bounds__(QF8_THREADS) void quantize_rows_e4m3_kernel(
+    const bf16* __restrict__ w, long wstride, unsigned char* __restrict__ q,
+    float* __restrict__ scale, int K) {
+  const long row = blockIdx.x;
+  quantize_row_e4m3<VEC>((const short*)w + row * wstride, q + row * K, scale,
+                         row, K);
+}
+
+// a stack w [E, N, K] with expert stride estride (elements): workgroup (n, e)
+// takes row n of expert e; q [E, N, K] and scale [E, N] are contiguous.  Only
+// the row -> address mapping differs from the 2-D kernel.
+template <int VEC>
+__global__ __launch_bounds__(QF8_THREADS) void quantize_stack_e4m3_kernel(
+    const bf16* __restrict__ w, long estride, long wstride,
+    unsigned char* __restrict__ q, float* __restrict__ scale, int N, int K) {
+  const long row = (long)blockIdx.y * N + blockIdx.x;
+  quantize_row_e4m3<VEC>(
+      (const short*)w + blockIdx.y * estride + blockIdx.x * wstride,
+      q + row * K, scale, row, K);
+}
+
 // in-place form: q [N, K] (one byte per element, contiguous) and scale
 // fp32 [N] are caller-owned, so their addresses survive a captured graph
+// w [E, N, K] bf16 with stride(2) == 1 and any row and expert stride (an
+// expert stack of views into one flat buffer): q [E, N, K], scale [E, N], one
+// launch; each [N, K] slice is what the 2-D form gives
+static void quantize_stack_e4m3_(const torch::Tensor& w, const torch::Tensor& q,
+                                 const torch::Tensor& scale) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+              w.stride(2) == 1, "w must be bf16 [E, N, K] with stride(2) == 1");
+  const long E = w.size(0), N = w.size(1), K = w.size(2);
+  TORCH_CHECK(q.is_cuda() && q.element_size() == 1 && q.dim() == 3 &&
+              q.size(0) == E && q.size(1) == N && q.size(2) == K &&
+              q.is_contiguous(),
+              "q must be contiguous [E, N, K] with one byte per element");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == torch::kFloat32 &&
+              scale.is_contiguous() && scale.numel() == E * N,
+              "scale must be contiguous fp32 [E, N]");
+  TORCH_CHECK(K < (1L << 31) && N < (1L << 31) && E < 65536);
+  if (E == 0 || N == 0 || K == 0) return;
+  const long wstride = N > 1 ? w.stride(1) : K;
+  const long estride = E > 1 ? w.stride(0) : 0;
+  const bool vec = K % 8 == 0 && wstride % 8 == 0 && estride % 8 == 0 &&
+                   (uintptr_t)w.data_ptr() % 16 == 0 &&
+                   (uintptr_t)q.data_ptr() % 8 == 0;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)N, (unsigned)E), dim3(QF8_THREADS),
+      0, cur_stream(), (const bf16*)w.data_ptr(), estride, wstride,
+      (unsigned char*)q.data_ptr(), scale.data_ptr<float>(), (int)N, (int)K);
+  };
+  if (vec) launch(quantize_stack_e4m3_kernel<8>);
+  else launch(quantize_stack_e4m3_kernel<1>);
+  CHECK_CUDA_OK();
+}
+
 void quantize_rows_e4m3_(torch::Tensor w, torch::Tensor q, torch::Tensor scale) {
+  if (w.dim() == 3) return quantize_stack_e4m3_(w, q, scale);
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
               w.dim() == 2 && w.stride(1) == 1,
               "w must be bf16 [N, K] with stride(1) == 1");
@@ -91,10 +145,10 @@ void quantize_rows_e4m3_(torch::Tensor w, torch::Tensor q, torch::Tensor scale) 
 }
 
 std::vector<torch::Tensor> quantize_rows_e4m3(torch::Tensor w) {
-  TORCH_CHECK(w.dim() == 2);
-  auto q = torch::empty({w.size(0), w.size(1)},
-                        w.options().dtype(at::kFloat8_e4m3fn));
-  auto scale = torch::empty({w.size(0)}, w.options().dtype(torch::kFloat32));
+  TORCH_CHECK(w.dim() == 2 || w.dim() == 3);
+  auto q = torch::empty(w.sizes(), w.options().dtype(at::kFloat8_e4m3fn));
+  auto scale = torch::empty(w.sizes().slice(0, w.dim() - 1),
+                            w.options().dtype(torch::kFloat32));
   quantize_rows_e4m3_(w, q, scale);
   return {q, scale};
 }

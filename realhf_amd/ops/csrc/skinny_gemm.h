@@ -68,7 +68,26 @@ DEVINL void sg_reduce_store(const float* __restrict__ parts, long slab,
 typedef __attribute__((ext_vector_type(4))) int int4v;  // one 16-byte W load
 typedef __attribute__((ext_vector_type(2))) float float2v;
 
-DEVINL bf16x8 sg_e4m3x8_to_bf16(int lo, int hi);
+// e4m3 -> bf16 for the FP8 weight streams (skinny_gemm.hip "Conversion",
+// moe_decode.hip): v_cvt_pk_f32_fp8, then the upper 16 bits of each f32
+DEVINL unsigned sg_bf16_pair(float lo, float hi) {
+  return (__builtin_bit_cast(unsigned, lo) >> 16) |
+         (__builtin_bit_cast(unsigned, hi) & 0xffff0000u);
+}
+
+// 8 consecutive e4m3 bytes (lo = bytes 0..3, hi = 4..7) -> bf16x8, in order
+DEVINL bf16x8 sg_e4m3x8_to_bf16(int lo, int hi) {
+  const float2v p0 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false);
+  const float2v p1 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+  const float2v p2 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false);
+  const float2v p3 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+  int4v u;
+  u[0] = (int)sg_bf16_pair(p0[0], p0[1]);
+  u[1] = (int)sg_bf16_pair(p1[0], p1[1]);
+  u[2] = (int)sg_bf16_pair(p2[0], p2[1]);
+  u[3] = (int)sg_bf16_pair(p3[0], p3[1]);
+  return __builtin_bit_cast(bf16x8, u);
+}
 
 #define SG_XV 8  // x vectors a thread stages through registers
 

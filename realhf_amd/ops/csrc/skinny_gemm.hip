@@ -339,25 +339,7 @@ torch::Tensor skinny_gemm(torch::Tensor x, torch::Tensor w,
 // applied once per output in the epilogue, before the fp32 partial is
 // stored: the slabs mean what the bf16 kernel's slabs mean and every slab
 // consumer (sg_combine_kernel, rope_qkv_decode, add_rmsnorm, swiglu/geglu)
-// is unchanged.
-DEVINL unsigned sg_bf16_pair(float lo, float hi) {
-  return (__builtin_bit_cast(unsigned, lo) >> 16) |
-         (__builtin_bit_cast(unsigned, hi) & 0xffff0000u);
-}
-
-// 8 consecutive e4m3 bytes (lo = bytes 0..3, hi = 4..7) -> bf16x8, in order
-DEVINL bf16x8 sg_e4m3x8_to_bf16(int lo, int hi) {
-  const float2v p0 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false);
-  const float2v p1 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
-  const float2v p2 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false);
-  const float2v p3 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
-  int4v u;
-  u[0] = (int)sg_bf16_pair(p0[0], p0[1]);
-  u[1] = (int)sg_bf16_pair(p1[0], p1[1]);
-  u[2] = (int)sg_bf16_pair(p2[0], p2[1]);
-  u[3] = (int)sg_bf16_pair(p3[0], p3[1]);
-  return __builtin_bit_cast(bf16x8, u);
-}
+// is unchanged.  (sg_e4m3x8_to_bf16: skinny_gemm.h, shared with moe_decode.hip)
 
 // NB x 64-deep k body (sg_slice<true>): 2*NB MFMAs per batch of NB q loads
 template <int NB>

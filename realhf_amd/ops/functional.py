@@ -42,7 +42,10 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        down and the slab combine (+ residual), no host sync;
                        moe_decode_supported is its one gate, moe_decode_ref
                        the CPU form (REALHF_AMD_NO_MOE_DECODE=1: the
-                       training route MoELayer.forward instead)
+                       training route MoELayer.forward instead); fp8 = the
+                       (q, scale) pairs of the gate, up and down stacks:
+                       the routed kernels stream e4m3 codes
+                       (REALHF_AMD_NO_FP8_MOE=1: no expert pairs are built)
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -1039,14 +1042,33 @@ def moe_down_splitk(idim: int) -> int:
     return -(-idim // MOE_DECODE_KSLICE)
 
 
+def fp8_moe_enabled() -> bool:
+    """A MoE model under weight_quant="fp8_e4m3" decodes its experts from
+    e4m3 (q, scale) stacks unless REALHF_AMD_NO_FP8_MOE=1 (read at call
+    time): then the session builds no expert pairs and the experts decode
+    on the bf16 moe_decode kernels, the A/B baseline."""
+    return os.environ.get("REALHF_AMD_NO_FP8_MOE") != "1"
+
+
+def moe_fp8_dequant(fp8):
+    """The fp32 (gate, up, down) stacks that the three (q, scale) pairs
+    stand for: q.float() * scale[..., None]."""
+    return tuple(q.float() * s[..., None] for q, s in fp8)
+
+
 def moe_experts_decode(h, idx, wts, wg, wu, wd, residual=None, act=None,
-                       ws=None):
+                       ws=None, fp8=None):
     """The expert half of moe_decode for given routing: idx [M, k] int32
     (distinct experts per row), wts [M, k] fp32.  act / ws: caller-owned
-    [k, M, I] bf16 and fp32 slab workspace (default: the global buffers)."""
+    [k, M, I] bf16 and fp32 slab workspace (default: the global buffers).
+    fp8 = ((qg, sg), (qu, su), (qd, sd)) from quantize_rows_e4m3 of the
+    three stacks: stream the e4m3 codes instead (moe_gate_up_swiglu_fp8,
+    moe_down_fp8); wg / wu / wd are then not read."""
     from realhf_amd.base.constants import get_global_memory_buffer
 
     C = _ops.require_hip()
+    if fp8 is not None:
+        wd = fp8[2][0]
     k, hid, idim = idx.shape[1], wd.shape[1], wd.shape[2]
     splitk = moe_down_splitk(idim)
     if ws is None:
@@ -1057,26 +1079,40 @@ def moe_experts_decode(h, idx, wts, wg, wu, wd, residual=None, act=None,
         act = get_global_memory_buffer().get_tensor(
             (k * 16 * idim,), torch.bfloat16, "moe_decode_act"
         )[:k * h.shape[0] * idim]
-    act = C.moe_gate_up_swiglu(h, idx, wg, wu, act)
-    slabs = C.moe_down(act, idx, wts, wd, ws, splitk)
+    if fp8 is not None:
+        (qg, sg), (qu, su), (qd, sd) = fp8
+        act = C.moe_gate_up_swiglu_fp8(h, idx, qg, sg, qu, su, act)
+        slabs = C.moe_down_fp8(act, idx, wts, qd, sd, ws, splitk)
+    else:
+        act = C.moe_gate_up_swiglu(h, idx, wg, wu, act)
+        slabs = C.moe_down(act, idx, wts, wd, ws, splitk)
     if residual is not None:
         residual = residual.contiguous()
     return C.moe_combine(slabs, h, residual)
 
 
 def moe_decode(h, router_w, wg, wu, wd, top_k: int, norm_topk: bool,
-               residual=None):
+               residual=None, fp8=None):
     """A MoE layer's MLP (+ residual) for M <= 16 bf16 rows on the HIP
     kernels: moe_route_decode, moe_gate_up_swiglu, moe_down and the slab
     combine, four launches and no host sync.  wg / wu [E, I, H] and wd
     [E, H, I] are expert stacks of contiguous rows (any expert stride).
-    Off the GPU: moe_decode_ref."""
+    fp8: the three (q, scale) pairs of gate, up and down; the experts then
+    run on the FP8 kernels.  Off the GPU: moe_decode_ref, with fp8 on the
+    dequantised stacks (the MoE twin of fp8_linear_ref), so the weights in
+    use are the quantized ones either way."""
     if not _ops.use_hip(h):
+        if fp8 is not None:  # in fp32 (or h's wider type), as fp8_linear_ref
+            ct = torch.promote_types(h.dtype, torch.float32)
+            return moe_decode_ref(
+                h.to(ct), router_w.to(ct),
+                *(w.to(ct) for w in moe_fp8_dequant(fp8)), top_k, norm_topk,
+                None if residual is None else residual.to(ct)).to(h.dtype)
         return moe_decode_ref(h, router_w, wg, wu, wd, top_k, norm_topk,
                               residual)
     C = _ops.require_hip()
     idx, wts = C.moe_route_decode(h, router_w, top_k, norm_topk)
-    return moe_experts_decode(h, idx, wts, wg, wu, wd, residual)
+    return moe_experts_decode(h, idx, wts, wg, wu, wd, residual, fp8=fp8)
 
 
 # ---------------------------------------------------------------------------
@@ -1089,15 +1125,17 @@ def quantize_rows_e4m3_ref(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]
     """(q [N, K] float8_e4m3fn, scale [N] fp32) with scale = amax / 448 per
     row (1 for an all-zero row) and q = rne_e4m3(float(w) / scale).  The
     fixed definition the HIP quantizer matches bit for bit.  Rows with
-    non-finite weights get no special handling."""
+    non-finite weights get no special handling.  A stack [E, N, K] gives
+    q [E, N, K] and scale [E, N], each [N, K] slice on its own."""
     wf = w.float()
-    amax = wf.abs().amax(dim=1)
+    amax = wf.abs().amax(dim=-1)
     scale = torch.where(amax == 0, torch.ones_like(amax), amax / E4M3_MAX)
-    return (wf / scale[:, None]).to(torch.float8_e4m3fn), scale
+    return (wf / scale[..., None]).to(torch.float8_e4m3fn), scale
 
 
 def quantize_rows_e4m3(w: torch.Tensor, out=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Quantize bf16 w [N, K] (stride(1) == 1, any row stride) per row.
+    """Quantize bf16 w [N, K] (stride(1) == 1, any row stride) per row, or
+    an expert stack [E, N, K] (any uniform expert stride) in one launch.
     out = (q, scale) writes into caller-owned buffers (stable addresses for
     a captured graph) and returns them."""
     if _ops.use_hip(w):

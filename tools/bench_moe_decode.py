@@ -12,6 +12,10 @@
 2. generate() of a tiny mixtral: kernels under the captured graph, kernels
    eager, and the kill switch (eager: it cannot be captured).
 
+--fp8 [--shape NAME] runs instead the same layers, M and rotating inputs with
+e4m3 expert pairs (moe_gate_up_swiglu_fp8, moe_down_fp8) against the bf16
+expert kernels, alternating in one run; TB/s then counts code bytes.
+
 Every figure is min / median / max over --repeats timed windows; the arms of
 a comparison alternate inside each repeat.  The training route syncs with
 the host in every call, so all arms are timed by the wall clock."""
@@ -76,6 +80,47 @@ def make_layer(H, I, E, k):
         take(f"1.mlp.experts.{e}.up.weight", I, H, 1 / math.sqrt(H))
         take(f"1.mlp.experts.{e}.down.weight", H, I, 1 / math.sqrt(I))
     return MoELayer(cfg, 1, params, tp_size=1).eval()
+
+
+@torch.no_grad()
+def bench_layer_fp8(a):
+    """--fp8: the same layers, inputs and M with e4m3 expert pairs installed
+    (moe_gate_up_swiglu_fp8, moe_down_fp8) against the bf16 kernels in the
+    same run.  TB/s counts the code bytes of the experts in use."""
+    from realhf_amd.ops import functional as ops
+
+    print(f"one MoE layer's decode MLP, FP8 against bf16 expert kernels, "
+          f"iters={a.iters} x repeats={a.repeats}, {a.inputs} rotating inputs; "
+          "us per call (min / median / max)")
+    print(f"{'shape':16} {'M':>3} {'fp8 kernels us':>26} {'bf16 kernels us':>26} "
+          f"{'ratio':>6} {'experts':>8} {'TB/s':>6}")
+    for name, H, I, E, k in SHAPES:
+        if a.shape not in ("all", name):
+            continue
+        torch.manual_seed(0)
+        layer = make_layer(H, I, E, k)
+        pairs = tuple(ops.quantize_rows_e4m3(w) for w in layer.decode_stacks())
+        for M in (1, 4, 16):
+            hs = [torch.randn(M, H, device="cuda").bfloat16()
+                  for _ in range(a.inputs)]
+            res = torch.randn(M, H, device="cuda").bfloat16()
+            n_active = statistics.mean(
+                C.moe_route_decode(h, layer.router.weight, k, True)[0]
+                .unique().numel() for h in hs)
+            fn = lambda i: layer.decode(hs[i % a.inputs], residual=res)
+            t_new, t_old = [], []
+            for _ in range(a.repeats):
+                layer.fp8 = pairs
+                t_new.append(window(fn, a.iters, a.iters // 10))
+                layer.fp8 = ()
+                t_old.append(window(fn, a.iters, a.iters // 10))
+            fmt = lambda s: f"{s[0]:8.1f}/{s[1]:8.1f}/{s[2]:8.1f}"
+            new, old = stats(t_new), stats(t_old)
+            tbs = n_active * 3 * H * I / (new[1] * 1e-6) / 1e12
+            print(f"{name:16} {M:3d} {fmt(new)} {fmt(old)} "
+                  f"{old[1] / new[1]:6.2f} {n_active:8.1f} {tbs:6.2f}")
+        del layer, pairs
+        torch.cuda.empty_cache()
 
 
 @torch.no_grad()
@@ -152,6 +197,14 @@ if __name__ == "__main__":
     p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--inputs", type=int, default=16)
     p.add_argument("--new-tokens", type=int, default=64)
+    p.add_argument("--fp8", action="store_true",
+                   help="FP8 expert kernels against the bf16 kernels, only")
+    p.add_argument("--shape", default="all",
+                   choices=["all"] + [s[0] for s in SHAPES],
+                   help="with --fp8: one shape per process")
     a = p.parse_args()
-    bench_layer(a)
-    bench_generate(a)
+    if a.fp8:
+        bench_layer_fp8(a)
+    else:
+        bench_layer(a)
+        bench_generate(a)
