@@ -32,6 +32,11 @@ class GenerationHyperparameters:
     # reads REALHF_AMD_GEN_KV_QUANT at generate() time (default "none");
     # anything else raises there.  Composes with weight_quant.
     kv_quant: Optional[str] = None
+    # Per-token sampler: None | "torch" | "hip".  None reads
+    # REALHF_AMD_GEN_SAMPLER at generate() time (default "torch"); anything
+    # else raises there.  "hip" draws one uniform per row and step instead
+    # of multinomial's draw, so one seed gives other tokens than "torch".
+    sampler: Optional[str] = None
 
 
 @dataclasses.dataclass

@@ -148,14 +148,16 @@ class DecodeGraph:
 
 WEIGHT_QUANT_MODES = ("none", "fp8_e4m3")
 KV_QUANT_MODES = ("none", "fp8_e4m3")
+SAMPLERS = ("torch", "hip")
 
 
-def _resolve_quant(gconfig, field: str, env: str, modes) -> str:
+def _resolve_quant(gconfig, field: str, env: str, modes,
+                   default: str = "none") -> str:
     """The requested mode: the gconfig field when set, else the environment
-    variable read now (default "none")."""
+    variable read now (default `default`)."""
     mode = getattr(gconfig, field)
     if mode is None:
-        mode = os.environ.get(env) or "none"
+        mode = os.environ.get(env) or default
     if mode not in modes:
         raise ValueError(
             f"{field} must be one of {modes} or None, got {mode!r}")
@@ -238,6 +240,33 @@ def effective_kv_quant(model: ReaLModel,
     return _effective_quant(
         model, resolve_kv_quant(gconfig), "kv_quant", kv_quant_blocker,
         "_kv_quant_warned", f"generating with {model.dtype} KV caches")
+
+
+def resolve_sampler(gconfig: GenerationHyperparameters) -> str:
+    """The requested per-token sampler (REALHF_AMD_GEN_SAMPLER when the
+    field is None, default "torch")."""
+    return _resolve_quant(gconfig, "sampler", "REALHF_AMD_GEN_SAMPLER",
+                          SAMPLERS, default="torch")
+
+
+def _sample_step(model, logits, gconfig, generator, want_mask):
+    """One step of sampler="hip": one uniform per row from the shared
+    generator, then ops.sample_logits, which is one kernel launch on the
+    GPU and sample_logits_ref with the same u elsewhere (the CPU, or a
+    top_k/top_p/dtype outside the kernel's forms: logged once per model),
+    so one seed gives one token stream either way."""
+    u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
+    if logits.is_cuda and not getattr(model, "_sampler_warned", False):
+        why = ops.sample_logits_unsupported(logits, gconfig.top_k,
+                                            gconfig.top_p, gconfig.greedy)
+        if why is not None:
+            logger.warning("sampler=hip: %s is outside the kernel's forms; "
+                           "sampling with the torch reference", why)
+            model._sampler_warned = True
+    # as in _sample_from_logits, greedy ignores the temperature
+    return ops.sample_logits(
+        logits, u, 1.0 if gconfig.greedy else gconfig.temperature,
+        gconfig.top_k, gconfig.top_p, gconfig.greedy, want_mask)
 
 
 class Fp8DecodeWeights:
@@ -484,7 +513,17 @@ def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
 
     last_idx = (cu_seqlens[1:].long() - 1)
     last_logits = logits[last_idx]  # [bs, vocab/tp]
-    last_logits = mappings.gather_from_tp_region(last_logits).float()
+    hip_sampler = resolve_sampler(gconfig) == "hip"
+
+    def sampler_input(x):
+        # the kernel reads bf16 rows as they are: no fp32 copy per step
+        x = mappings.gather_from_tp_region(x)
+        if hip_sampler and model.tp_size == 1 and x.dtype in (
+                torch.bfloat16, torch.float32):
+            return x
+        return x.float()
+
+    last_logits = sampler_input(last_logits)
 
     gen_tokens = torch.full((bs, max_new), pad_token_id, dtype=torch.long, device=device)
     gen_logprobs = torch.zeros(bs, max_new, dtype=torch.float32, device=device)
@@ -526,8 +565,12 @@ def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
     for t in range(max_new):
         if eos_token_id is not None and t < gconfig.min_new_tokens:
             cur_logits[:, eos_token_id] = float("-inf")
-        tokens, logp, smask = _sample_from_logits(
-            cur_logits, gconfig, generator, return_mask=want_mask)
+        if hip_sampler:
+            tokens, logp, smask = _sample_step(model, cur_logits, gconfig,
+                                               generator, want_mask)
+        else:
+            tokens, logp, smask = _sample_from_logits(
+                cur_logits, gconfig, generator, return_mask=want_mask)
         if want_mask:
             step_masks.append(smask)
         tokens = torch.where(done, torch.full_like(tokens, pad_token_id), tokens)
@@ -552,8 +595,7 @@ def _generate(model, sess, packed_prompts, cu_seqlens, prompt_lens, max_prompt,
                 decoder._capture_failed = True
                 torch.cuda.synchronize()
         logits_step = decoder.step(tokens, cache_seqlens)
-        logits_step = mappings.gather_from_tp_region(logits_step).float()
-        cur_logits = logits_step
+        cur_logits = sampler_input(logits_step)
 
     gmax = int(gen_lengths.max())
     logits_mask = None

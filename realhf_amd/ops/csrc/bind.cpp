@@ -156,6 +156,12 @@ torch::Tensor moe_down_fp8(torch::Tensor act, torch::Tensor idx,
                            torch::Tensor wts, torch::Tensor qd,
                            torch::Tensor sd, torch::Tensor out32_ws,
                            long splitk);
+// Decode sampler: temperature, top-k, top-p, draw and log-prob, one workgroup
+// per row -> (tokens int64 [bs], logp fp32 [bs], mask bool [bs, V] or empty)
+std::vector<torch::Tensor> sample_logits(torch::Tensor logits, torch::Tensor u,
+                                         double inv_temperature, long top_k,
+                                         double top_p, bool greedy,
+                                         bool want_mask);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -230,4 +236,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_down_fp8", &moe_down_fp8);
   m.def("moe_combine", &moe_combine, py::arg("slabs"), py::arg("like"),
         py::arg("residual") = py::none());
+  m.def("sample_logits", &sample_logits, py::arg("logits"), py::arg("u"),
+        py::arg("inv_temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("greedy"), py::arg("want_mask"));
 }

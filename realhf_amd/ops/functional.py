@@ -46,6 +46,12 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        (q, scale) pairs of the gate, up and down stacks:
                        the routed kernels stream e4m3 codes
                        (REALHF_AMD_NO_FP8_MOE=1: no expert pairs are built)
+  sample_logits      — the per-token decode sampler in one launch per step:
+                       temperature, top-k (radix select), top-p (LDS sort +
+                       scan), inverse-CDF draw from one uniform per row,
+                       the token's log-prob and the optional removed-entry
+                       mask; sample_logits_unsupported is its gate,
+                       sample_logits_ref the CPU form and the oracle
 
 All torch reference paths are fp32-upcast where the reference math is fp32.
 """
@@ -793,6 +799,109 @@ def vocab_logprobs(logits, labels, *, vocab_start=0, group=None,
     [n] log-sum-exp for backward."""
     return _VocabLogProbFn.apply(logits, labels.long(), int(vocab_start), group,
                                  int(ignore_index))
+
+
+# ---------------------------------------------------------------------------
+# Decode sampler: temperature -> top-k -> top-p -> inverse-CDF draw + log-prob
+# ---------------------------------------------------------------------------
+SAMPLE_MAX_K = 1024  # candidates the kernel's select form sorts in LDS
+
+
+def _sample_k_p(V: int, top_k: int, top_p: float) -> Tuple[int, float]:
+    """(k, p) with the "off" values folded: top_k <= 0 or >= V is V, a
+    top_p outside (0, 1) is 1."""
+    return (top_k if 0 < top_k < V else V,
+            top_p if 0.0 < top_p < 1.0 else 1.0)
+
+
+def sample_logits_ref(logits, u, temperature=1.0, top_k=0, top_p=1.0,
+                      greedy=False, want_mask=False):
+    """(tokens int64 [bs], logp [bs], mask bool [bs, V] or None) from
+    logits [bs, V] and one uniform u [bs] in [0, 1) per row, in fp32 (fp64
+    for fp64 logits), with x = logits / temperature:
+
+    - greedy: the argmax, lowest index among equals; logp = x_tok - lse(x);
+    - candidates: the k largest x, ordered by (value descending, index
+      ascending), -inf entries last and never kept;
+    - nucleus: with e_i = exp(x_i - x_0) and Z1 = sum e, candidate i is kept
+      iff its exclusive prefix sum is <= top_p * Z1 (candidate 0 always);
+      the kept set is a prefix of length m, Z2 = sum_{i<m} e_i;
+    - draw: the first kept i whose inclusive prefix sum exceeds u * Z2,
+      clamped to m - 1;
+    - with nothing to filter (k >= V, top_p >= 1) the order is immaterial
+      to the distribution and the draw walks the row in index order;
+    - logp is under the unfiltered row (x_tok - lse) unless want_mask, then
+      log(e_tok / Z2) together with mask, True = entry removed."""
+    ft = torch.float64 if logits.dtype == torch.float64 else torch.float32
+    x = logits.to(ft) * (1.0 / max(temperature, 1e-5))
+    u = u.to(ft)
+    V = x.shape[-1]
+    vals, order = torch.sort(x, dim=-1, descending=True, stable=True)
+    lse = torch.logsumexp(x, dim=-1)
+    if greedy:
+        return order[:, 0], vals[:, 0] - lse, None
+    k, p = _sample_k_p(V, top_k, top_p)
+    finite = x > float("-inf")
+    if k >= V and p >= 1.0:
+        cum = (x - vals[:, :1]).exp().cumsum(-1)
+        z2 = cum[:, -1]
+        last = (finite * torch.arange(V, device=x.device)).amax(-1)
+        tokens = torch.minimum((cum <= (u * z2).unsqueeze(-1)).sum(-1), last)
+        x_tok = x.gather(-1, tokens.unsqueeze(-1)).squeeze(-1)
+        if want_mask:
+            return tokens, (x_tok - vals[:, 0]) - z2.log(), ~finite
+        return tokens, x_tok - lse, None
+    vals, order = vals[:, :k], order[:, :k]
+    e = (vals - vals[:, :1]).exp()
+    cum = e.cumsum(-1)
+    kept = (vals > float("-inf")) & ((cum - e <= p * cum[:, -1:]) | (p >= 1.0))
+    kept[:, 0] = True
+    m = kept.long().cumprod(-1).sum(-1)  # length of the kept prefix
+    z2 = cum.gather(-1, (m - 1).unsqueeze(-1)).squeeze(-1)
+    sel = torch.minimum((cum <= (u * z2).unsqueeze(-1)).sum(-1), m - 1)
+    tokens = order.gather(-1, sel.unsqueeze(-1)).squeeze(-1)
+    x_tok = vals.gather(-1, sel.unsqueeze(-1)).squeeze(-1)
+    if not want_mask:
+        return tokens, x_tok - lse, None
+    mask = torch.ones_like(x, dtype=torch.bool)
+    mask.scatter_(1, order,
+                  torch.arange(k, device=x.device).unsqueeze(0) >= m.unsqueeze(-1))
+    return tokens, (x_tok - vals[:, 0]) - z2.log(), mask
+
+
+def sample_logits_unsupported(logits, top_k: int, top_p: float,
+                              greedy: bool) -> Optional[str]:
+    """Why the sample_logits kernel does not take this call (None if it
+    does): it has a select form (k <= SAMPLE_MAX_K) and a full form (no
+    filter at all, or greedy) for bf16 and fp32 rows."""
+    if logits.dtype not in (torch.bfloat16, torch.float32):
+        return f"{logits.dtype} logits"
+    k, p = _sample_k_p(logits.shape[-1], top_k, top_p)
+    if greedy or (k >= logits.shape[-1] and p >= 1.0):
+        return None
+    if k >= logits.shape[-1]:
+        return "top_p < 1 without top_k"
+    if k > SAMPLE_MAX_K:
+        return f"top_k {k} > {SAMPLE_MAX_K}"
+    return None
+
+
+def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0,
+                  greedy=False, want_mask=False):
+    """sample_logits_ref's result from one kernel launch where the logits
+    are on the GPU and sample_logits_unsupported names no reason; the
+    reference otherwise."""
+    if _ops.use_hip(logits) and sample_logits_unsupported(
+            logits, top_k, top_p, greedy) is None:
+        C = _ops.require_hip()
+        k, p = _sample_k_p(logits.shape[-1], top_k, top_p)
+        tokens, logp, mask = C.sample_logits(
+            logits.contiguous(), u.float().contiguous(),
+            1.0 / max(temperature, 1e-5), k, p, greedy,
+            want_mask and not greedy)
+        return tokens, logp, (mask if want_mask and not greedy else None)
+    return sample_logits_ref(logits, u, temperature, top_k, top_p, greedy,
+                             want_mask)
 
 
 # ---------------------------------------------------------------------------
