@@ -253,8 +253,8 @@ def _sample_step(model, logits, gconfig, generator, want_mask):
     """One step of sampler="hip": one uniform per row from the shared
     generator, then ops.sample_logits, which is one kernel launch on the
     GPU and sample_logits_ref with the same u elsewhere (the CPU, or a
-    top_k/top_p/dtype outside the kernel's forms: logged once per model),
-    so one seed gives one token stream either way."""
+    dtype or top_k range that sample_logits_unsupported names: logged once
+    per model), so one seed gives one token stream either way."""
     u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
     if logits.is_cuda and not getattr(model, "_sampler_warned", False):
         why = ops.sample_logits_unsupported(logits, gconfig.top_k,

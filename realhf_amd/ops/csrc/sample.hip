@@ -22,12 +22,18 @@
 //      sums for the top-p cut and the inverse CDF;
 //   5. optionally one more pass writes the mask row: removed iff comp is
 //      below the last kept candidate's.
+// Search form (k > 1024, which top_p without top_k is): no sort.  The cut
+// and the draw are each "the candidate whose interval of the running mass
+// holds a target", found by the same radix descent over comp with mass
+// summed per bin next to the counts.  Mass is a 64-bit integer, exp(x - max)
+// in units of 2^-39, so the LDS atomics that sum it give one result in any
+// order and every comparison is exact.
 // Full form (nothing filtered, or greedy): each lane owns a contiguous chunk
 // of the row, so a scan of the chunk sums and a walk inside one chunk give
 // the inverse CDF in index order; greedy is a (max, lowest index) reduction.
 //
-// No scratch, no float atomics, every reduction in a fixed order: results
-// are bitwise reproducible.
+// No scratch, no float atomics, every float reduction in a fixed order:
+// results are bitwise reproducible.
 #include "common.h"
 
 #include <cstdint>
@@ -266,6 +272,44 @@ template <typename T, bool REG> struct SmpRow {
   }
 };
 
+// The mask row: True = removed, that is after the last kept candidate in
+// (value descending, index ascending).
+template <typename T, bool REG>
+DEVINL void smp_store_mask(SmpRow<T, REG>& r, bool* mr, u64 last) {
+  constexpr int VEC = SmpVec<T>::N;
+  const unsigned lkey = (unsigned)(last >> SMP_IDX_BITS);
+  const int lidx = (int)(SMP_IDX_MASK - (unsigned)(last & SMP_IDX_MASK));
+  auto removed = [&](unsigned key, int i) {
+    return key < lkey || (key == lkey && i > lidx);
+  };
+  // the vectors of the logits row are VEC-byte aligned in the mask row
+  // when both rows start equally far from such a boundary
+  const bool vec_ok = ((uintptr_t)(mr + r.head) & (VEC - 1)) == 0;
+  r.each_vec(
+      [&](unsigned key, int i) { mr[i] = removed(key, i); },
+      [&](const unsigned* kk, int i0) {
+        unsigned char b[VEC];
+        #pragma unroll
+        for (int j = 0; j < VEC; j++) b[j] = removed(kk[j], i0 + j);
+        if (vec_ok) {
+          if constexpr (VEC == 8) {
+            u64 w = 0;
+            #pragma unroll
+            for (int j = 0; j < 8; j++) w |= (u64)b[j] << (8 * j);
+            *(u64*)(mr + i0) = w;
+          } else {
+            unsigned w = 0;
+            #pragma unroll
+            for (int j = 0; j < 4; j++) w |= (unsigned)b[j] << (8 * j);
+            *(unsigned*)(mr + i0) = w;
+          }
+        } else {
+          #pragma unroll
+          for (int j = 0; j < VEC; j++) mr[i0 + j] = b[j];
+        }
+      });
+}
+
 template <typename T, bool REG>
 __global__ __launch_bounds__(SMP_THREADS) void sample_select_kernel(
     const T* __restrict__ logits, const float* __restrict__ u,
@@ -413,41 +457,219 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_select_kernel(
   }
 
   // ---- mask row: True = removed ----
-  if (mask != nullptr) {
-    const unsigned lkey = (unsigned)(sh_last >> SMP_IDX_BITS);
-    const int lidx = (int)(SMP_IDX_MASK - (unsigned)(sh_last & SMP_IDX_MASK));
-    // after the last kept candidate in (value descending, index ascending)
-    auto removed = [&](unsigned key, int i) {
-      return key < lkey || (key == lkey && i > lidx);
-    };
-    bool* mr = mask + row * (long)V;
-    // the vectors of the logits row are VEC-byte aligned in the mask row
-    // when both rows start equally far from such a boundary
-    const bool vec_ok = ((uintptr_t)(mr + r.head) & (VEC - 1)) == 0;
-    r.each_vec(
-        [&](unsigned key, int i) { mr[i] = removed(key, i); },
-        [&](const unsigned* kk, int i0) {
-          unsigned char b[VEC];
-          #pragma unroll
-          for (int j = 0; j < VEC; j++) b[j] = removed(kk[j], i0 + j);
-          if (vec_ok) {
-            if constexpr (VEC == 8) {
-              u64 w = 0;
-              #pragma unroll
-              for (int j = 0; j < 8; j++) w |= (u64)b[j] << (8 * j);
-              *(u64*)(mr + i0) = w;
-            } else {
-              unsigned w = 0;
-              #pragma unroll
-              for (int j = 0; j < 4; j++) w |= (unsigned)b[j] << (8 * j);
-              *(unsigned*)(mr + i0) = w;
-            }
-          } else {
-            #pragma unroll
-            for (int j = 0; j < VEC; j++) mr[i0 + j] = b[j];
-          }
-        });
+  if (mask != nullptr) smp_store_mask(r, mask + row * (long)V, sh_last);
+}
+
+// ---------------------------------------------------------------------------
+// Search form: top_p without top_k, and k > SMP_MAX_K
+// ---------------------------------------------------------------------------
+// An element's mass, exp(x - M) in units of 2^-39, M the row max: at most
+// 2^39 each, so fewer than 2^24 of them sum below 2^63.  Integer sums do not
+// depend on their order, which is what lets mass go through LDS atomics.
+#define SMP_MASS_ONE 549755813888.f  // 2^39
+
+DEVINL u64 smp_mass(unsigned key, float M) {
+  const float x = smp_unkey(key);
+  return x > -INFINITY ? (u64)(__expf(x - M) * SMP_MASS_ONE) : 0ull;
+}
+
+DEVINL u64 smp_block_sum(u64 v, u64* red) {
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += smp_shfl_xor(v, off);
+  __syncthreads();
+  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  u64 r = red[0];
+  #pragma unroll
+  for (int w = 1; w < SMP_NWAVES; w++) r += red[w];
+  return r;
+}
+DEVINL u64 smp_block_min(u64 v, u64* red) {
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const u64 o = smp_shfl_xor(v, off);
+    v = o < v ? o : v;
   }
+  __syncthreads();
+  if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  u64 r = red[0];
+  #pragma unroll
+  for (int w = 1; w < SMP_NWAVES; w++) r = red[w] < r ? red[w] : r;
+  return r;
+}
+
+struct SmpSearchLds {
+  unsigned cnt[SMP_HIST_COPIES * 256];
+  u64 mass[SMP_HIST_COPIES * 256];
+  u64 above, comp, q;
+  unsigned digit, found;
+};
+struct SmpFound {
+  u64 comp;   // the element found
+  u64 above;  // weight of the candidates strictly before it
+  u64 q;      // its own mass (MASS only)
+};
+
+// Radix search, 8 bits per pass from the top digit of comp, among the
+// candidates with comp >= lo, each weighing its mass (MASS) or 1: finds the
+// candidate whose interval [above, above + weight) of the running weight in
+// candidate order holds `target`; the caller keeps target below the total.
+// With unit weights that is the candidate of rank target, counted from 0.
+// Per pass the candidates that share the digits found so far add to the
+// bins of their next digit (8 copies, spread by lane); 256 lanes fold the
+// copies, wave 0 scans the bins from 255 down and publishes the bin that
+// holds the target, the weight before it and the number of candidates in
+// it.  The descent ends at a bin of one candidate, after digit 0 at the
+// latest (comps are distinct): at most 7 passes, and one more that reads the
+// found candidate back.  A candidate of no mass is never found by mass.
+template <bool MASS, typename T, bool REG>
+DEVINL SmpFound smp_search(SmpRow<T, REG>& r, SmpSearchLds& s, u64 lo,
+                           u64 target, float M) {
+  const int tid = threadIdx.x;
+  unsigned* mycnt = s.cnt + (tid & (SMP_HIST_COPIES - 1)) * 256;
+  u64* mymass = s.mass + (tid & (SMP_HIST_COPIES - 1)) * 256;
+  u64 pre = 0, above = 0;
+  int shift = 56;
+  unsigned found;
+  do {
+    shift -= 8;
+    __syncthreads();
+    for (int i = tid; i < SMP_HIST_COPIES * 256; i += SMP_THREADS) {
+      s.cnt[i] = 0;
+      if constexpr (MASS) s.mass[i] = 0;
+    }
+    if (tid == 0) { s.digit = 0; s.found = 0; s.above = above; }
+    __syncthreads();
+    const u64 want = pre >> (shift + 8);
+    r.each([&](unsigned key, int idx) {
+      const u64 c = smp_comp(key, idx);
+      if (c >= lo && (c >> (shift + 8)) == want) {
+        const unsigned d = (unsigned)(c >> shift) & 255u;
+        atomicAdd(&mycnt[d], 1u);
+        if constexpr (MASS) atomicAdd(&mymass[d], smp_mass(key, M));
+      }
+    });
+    __syncthreads();
+    if (tid < 256) {  // fold the copies into the first
+      unsigned c = 0;
+      u64 m = 0;
+      #pragma unroll
+      for (int cp = 0; cp < SMP_HIST_COPIES; cp++) {
+        c += s.cnt[cp * 256 + tid];
+        if constexpr (MASS) m += s.mass[cp * 256 + tid];
+      }
+      s.cnt[tid] = c;
+      if constexpr (MASS) s.mass[tid] = m;
+    }
+    __syncthreads();
+    if (tid < WAVE) {  // lane l owns bins 255 - 4l .. 252 - 4l, largest first
+      const int b0 = 255 - 4 * tid;
+      unsigned c[4];
+      u64 w[4], tot = 0;
+      #pragma unroll
+      for (int j = 0; j < 4; j++) {
+        c[j] = s.cnt[b0 - j];
+        w[j] = MASS ? s.mass[b0 - j] : (u64)c[j];
+        tot += w[j];
+      }
+      const u64 incl = smp_wave_incl_scan(tot);
+      u64 ab = above + (incl - tot);
+      if (ab <= target && target < ab + tot) {  // at most one lane
+        #pragma unroll
+        for (int j = 0; j < 4; j++) {
+          if (ab <= target && target < ab + w[j]) {
+            s.digit = (unsigned)(b0 - j);
+            s.found = c[j];
+            s.above = ab;
+          }
+          ab += w[j];
+        }
+      }
+    }
+    __syncthreads();
+    pre |= (u64)s.digit << shift;
+    above = s.above;
+    found = s.found;
+  } while (found > 1 && shift > 0);
+
+  if (tid == 0) { s.comp = 0; s.q = 0; }
+  __syncthreads();
+  const u64 want = pre >> shift;
+  r.each([&](unsigned key, int idx) {
+    const u64 c = smp_comp(key, idx);
+    if (c >= lo && (c >> shift) == want) {  // one element
+      s.comp = c;
+      if constexpr (MASS) s.q = smp_mass(key, M);
+    }
+  });
+  __syncthreads();
+  return SmpFound{s.comp, above, s.q};
+}
+
+// Steps: load as the select form does; with k < V a rank search for the k-th
+// comp, below which nothing is a candidate; one pass for Z1, the candidates'
+// mass, and for the smallest finite candidate, which is the last kept one
+// when top_p keeps everything; with top_p < 1 a mass search for the
+// candidate whose interval holds top_p * Z1, the last kept one, Z2 the mass
+// down to it; a mass search among the kept for u * Z2, the token; the mask.
+template <typename T, bool REG>
+__global__ __launch_bounds__(SMP_THREADS) void sample_search_kernel(
+    const T* __restrict__ logits, const float* __restrict__ u,
+    long* __restrict__ tokens, float* __restrict__ logp,
+    bool* __restrict__ mask, int V, int k, float inv_t, float top_p) {
+  __shared__ SmpSearchLds s;
+  __shared__ float redf[SMP_NWAVES];
+  __shared__ u64 red64[SMP_NWAVES];
+  const long row = blockIdx.x;
+
+  SmpRow<T, REG> r;
+  float lm, ls;
+  r.load(logits + row * (long)V, V, inv_t, lm, ls);
+  const float M = smp_block_max(lm, redf);
+  float zrow;
+  smp_block_excl_scan(lm > -INFINITY ? ls * __expf(lm - M) : 0.f, redf, zrow);
+  float lse = M + logf(zrow);
+  asm volatile("" : "+v"(lse));  // as in the select form
+
+  u64 lo = 0;
+  if (k < V) lo = smp_search<false>(r, s, 0ull, (u64)(k - 1), M).comp;
+
+  const unsigned neginf = smp_key(-INFINITY);
+  u64 zl = 0, fl = ~0ull;
+  r.each([&](unsigned key, int idx) {
+    const u64 c = smp_comp(key, idx);
+    if (c >= lo && key > neginf) {
+      zl += smp_mass(key, M);
+      fl = c < fl ? c : fl;
+    }
+  });
+  const u64 z1 = smp_block_sum(zl, red64);
+  u64 last = smp_block_min(fl, red64);
+
+  u64 z2 = z1, tok;
+  if (last == ~0ull) {  // no finite entry: candidate 0 alone, as the reference
+    last = tok = smp_comp(neginf, 0);
+  } else {
+    // the maximum weighs 2^39, so z1 > 0 and the threshold is below z1
+    if (top_p < 1.f) {
+      const u64 thr = (u64)((double)top_p * (double)z1);
+      const SmpFound f = smp_search<true>(r, s, lo, thr < z1 ? thr : z1 - 1, M);
+      last = f.comp;
+      z2 = f.above + f.q;
+    }
+    const u64 t = (u64)((double)u[row] * (double)z2);
+    tok = smp_search<true>(r, s, last, t < z2 ? t : z2 - 1, M).comp;
+  }
+  if (threadIdx.x == 0) {
+    int idx = (int)(SMP_IDX_MASK - (unsigned)(tok & SMP_IDX_MASK));
+    if (idx >= V) idx = 0;
+    const float x = smp_unkey((unsigned)(tok >> SMP_IDX_BITS));
+    tokens[row] = idx;
+    logp[row] = mask != nullptr
+        ? (x - M) - logf((float)z2 * (1.f / SMP_MASS_ONE)) : x - lse;
+  }
+  if (mask != nullptr) smp_store_mask(r, mask + row * (long)V, last);
 }
 
 // ---------------------------------------------------------------------------
@@ -550,9 +772,8 @@ std::vector<torch::Tensor> sample_logits(torch::Tensor logits, torch::Tensor u,
               "sample_logits: u must be a contiguous fp32 [bs] GPU tensor");
   const long k = (top_k <= 0 || top_k > V) ? V : top_k;
   const bool full = greedy || (k >= V && top_p >= 1.0);
-  TORCH_CHECK(full || k <= SMP_MAX_K, "sample_logits: top_k ", k,
-              " with top_p ", top_p, " over ", V, " entries is not a form "
-              "this kernel takes (select: k <= 1024; full: k >= V, top_p >= 1)");
+  // more candidates than the select form sorts: the search form
+  const bool search = !full && k > SMP_MAX_K;
   auto tokens = torch::empty({bs}, logits.options().dtype(torch::kLong));
   auto logp = torch::empty({bs}, logits.options().dtype(torch::kFloat));
   auto mask = want_mask ? torch::empty({bs, V}, logits.options().dtype(torch::kBool))
@@ -572,6 +793,11 @@ std::vector<torch::Tensor> sample_logits(torch::Tensor logits, torch::Tensor u,
         dim3(SMP_THREADS), 0, cur_stream(), x, u.data_ptr<float>(),
         (long*)tokens.data_ptr<int64_t>(), logp.data_ptr<float>(), mp, (int)V,
         (float)inv_temperature, (int)greedy);
+    else if (search)
+      hipLaunchKernelGGL((sample_search_kernel<scalar_t, REG>), dim3((unsigned)bs),
+        dim3(SMP_THREADS), 0, cur_stream(), x, u.data_ptr<float>(),
+        (long*)tokens.data_ptr<int64_t>(), logp.data_ptr<float>(), mp, (int)V,
+        (int)k, (float)inv_temperature, (float)top_p);
     else
       hipLaunchKernelGGL((sample_select_kernel<scalar_t, REG>), dim3((unsigned)bs),
         dim3(SMP_THREADS), 0, cur_stream(), x, u.data_ptr<float>(),

@@ -48,7 +48,8 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
                        (REALHF_AMD_NO_FP8_MOE=1: no expert pairs are built)
   sample_logits      — the per-token decode sampler in one launch per step:
                        temperature, top-k (radix select), top-p (LDS sort +
-                       scan), inverse-CDF draw from one uniform per row,
+                       scan for k <= 1024, a radix search on integer mass
+                       beyond), inverse-CDF draw from one uniform per row,
                        the token's log-prob and the optional removed-entry
                        mask; sample_logits_unsupported is its gate,
                        sample_logits_ref the CPU form and the oracle
@@ -804,7 +805,9 @@ def vocab_logprobs(logits, labels, *, vocab_start=0, group=None,
 # ---------------------------------------------------------------------------
 # Decode sampler: temperature -> top-k -> top-p -> inverse-CDF draw + log-prob
 # ---------------------------------------------------------------------------
-SAMPLE_MAX_K = 1024  # candidates the kernel's select form sorts in LDS
+SAMPLE_MAX_K = 1024  # candidates the kernel's select form sorts in LDS; more
+# take its sort-free search form
+SAMPLE_REG_BYTES = 1024 * 8 * 16  # row bytes one workgroup holds in registers
 
 
 def _sample_k_p(V: int, top_k: int, top_p: float) -> Tuple[int, float]:
@@ -872,25 +875,30 @@ def sample_logits_ref(logits, u, temperature=1.0, top_k=0, top_p=1.0,
 def sample_logits_unsupported(logits, top_k: int, top_p: float,
                               greedy: bool) -> Optional[str]:
     """Why the sample_logits kernel does not take this call (None if it
-    does): it has a select form (k <= SAMPLE_MAX_K) and a full form (no
-    filter at all, or greedy) for bf16 and fp32 rows."""
+    does).  Every (top_k, top_p) has a form: select (k <= SAMPLE_MAX_K),
+    search (more candidates, which top_p without top_k is) or full (no
+    filter at all, or greedy), on bf16 and fp32 rows.  One range stays on
+    the reference although the kernel computes it: SAMPLE_MAX_K < top_k < V
+    over a row too long for the workgroup's registers (SAMPLE_REG_BYTES),
+    which every pass of the search re-reads.  Measured at [16, 128256] bf16,
+    top_k 4000, top_p 0.9: 378 us against the torch sampler's 274 us (its
+    topk), spread 1.4 % (docs/perf.md); with top_k off the same rows are
+    305 us against 752 us and stay on the kernel."""
     if logits.dtype not in (torch.bfloat16, torch.float32):
         return f"{logits.dtype} logits"
-    k, p = _sample_k_p(logits.shape[-1], top_k, top_p)
-    if greedy or (k >= logits.shape[-1] and p >= 1.0):
-        return None
-    if k >= logits.shape[-1]:
-        return "top_p < 1 without top_k"
-    if k > SAMPLE_MAX_K:
-        return f"top_k {k} > {SAMPLE_MAX_K}"
+    V = logits.shape[-1]
+    k, _ = _sample_k_p(V, top_k, top_p)
+    if (not greedy and SAMPLE_MAX_K < k < V
+            and V * logits.element_size() > SAMPLE_REG_BYTES):
+        return f"top_k {k} > {SAMPLE_MAX_K} over a row of {V} beyond the registers"
     return None
 
 
 def sample_logits(logits, u, temperature=1.0, top_k=0, top_p=1.0,
                   greedy=False, want_mask=False):
     """sample_logits_ref's result from one kernel launch where the logits
-    are on the GPU and sample_logits_unsupported names no reason; the
-    reference otherwise."""
+    are on the GPU and sample_logits_unsupported names no reason (any
+    top_k and top_p on bf16 or fp32 rows); the reference otherwise."""
     if _ops.use_hip(logits) and sample_logits_unsupported(
             logits, top_k, top_p, greedy) is None:
         C = _ops.require_hip()

@@ -5,7 +5,9 @@ sampling on [bs, V] bf16 logits, same process, alternating the two paths
 call by call, device events after warm-up.
 
 The torch path is timed as generate() runs it, the fp32 copy of the logits
-included; the kernel reads the bf16 rows and one torch.rand(bs).  Each path
+included; the kernel reads the bf16 rows and one torch.rand(bs).  Where
+sample_logits_unsupported names a reason the "hip" rows are sample_logits_ref,
+as sampler="hip" runs it, and the row says so.  Each path
 is timed as two interleaved series (a, b); the gap between the medians of a
 and b of the SAME path is the run-to-run spread that a difference has to
 exceed to mean anything.  Times are GPU time between events around eagerly
@@ -24,7 +26,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 BS = 16
 SHAPES = [32000, 128256]
-FILTERS = [(1000, 0.9), (200, 1.0), (0, 1.0)]  # top_k 0 = off
+FILTERS = [(1000, 0.9), (200, 1.0), (0, 1.0),  # top_k 0 = off
+           (0, 0.9), (0, 0.99), (4000, 0.9)]  # the kernel's search form
 
 
 def main():
@@ -41,7 +44,6 @@ def main():
     def call(hip, x, g):
         if hip:
             u = torch.rand(BS, generator=gen, device="cuda")
-            assert F.sample_logits_unsupported(x, g.top_k, g.top_p, False) is None
             return F.sample_logits(x, u, g.temperature, g.top_k, g.top_p)
         return _sample_from_logits(x.float(), g, gen)
 
@@ -76,7 +78,11 @@ def main():
         for _ in range(reps):
             for n in series:
                 series[n].append(timed(n.startswith("hip"), x, g))
-        row = {"bs": BS, "V": V, "top_k": k, "top_p": p}
+        # a request the gate names runs sample_logits_ref under sampler="hip"
+        why = F.sample_logits_unsupported(x, k, p, False)
+        row = {"bs": BS, "V": V, "top_k": k, "top_p": p, "hip_is_reference": why}
+        if why is not None:
+            print(f"{'':>20} hip = sample_logits_ref ({why})")
         for path in ("torch", "hip"):
             a, b = series[path + "_a"], series[path + "_b"]
             ma, mb = statistics.median(a), statistics.median(b)
