@@ -205,6 +205,10 @@ class PipelinableEngine(abc.ABC):
     ):
         ...
 
+    # True on engines whose forward implements head_logprobs; callers must
+    # not pass the keyword to one that leaves this False
+    supports_head_logprobs = False
+
     @abc.abstractmethod
     def forward(
         self,
@@ -212,6 +216,7 @@ class PipelinableEngine(abc.ABC):
         n_mbs: Optional[int] = None,
         post_hook: Optional[Callable] = None,
         aggregate_fn: Callable = None,
+        head_logprobs: Optional[float] = None,
     ):
         ...
 

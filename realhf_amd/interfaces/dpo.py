@@ -12,6 +12,7 @@ import torch
 
 from realhf_amd.api.data import SequenceSample
 from realhf_amd.api.model import Model, ModelInterface, register_interface
+from realhf_amd.interfaces.ppo import use_head_logprobs
 from realhf_amd.parallel.tp import packed_shifted_logprobs
 from realhf_amd.runtime.engine import sample_to_packed
 from realhf_amd.utils.functional import build_shift_one_indices
@@ -20,7 +21,12 @@ from realhf_amd.utils.functional import build_shift_one_indices
 def _seq_logps(logits, mb: SequenceSample) -> torch.Tensor:
     """Sum of answer-token logprobs per sequence -> [n_seqs_total]."""
     ids, cu, _ = sample_to_packed(mb)
-    logp = packed_shifted_logprobs(logits, cu, ids)
+    return _sum_seq_logps(packed_shifted_logprobs(logits, cu, ids), mb)
+
+
+def _sum_seq_logps(logp, mb: SequenceSample) -> torch.Tensor:
+    """Per-sequence sums of the [total - bs] next-token log-probs."""
+    ids, cu, _ = sample_to_packed(mb)
     shift = build_shift_one_indices(ids.shape[0], cu)
     if "prompt_mask" in mb.keys:
         mask = (~mb.data["prompt_mask"].bool()[shift]).float()
@@ -46,7 +52,12 @@ class DPOInterface(ModelInterface):
         def post_hook(logits, mb):
             return _seq_logps(logits, mb)
 
-        seqlogp = model.module.forward(data, n_mbs=n_mbs, post_hook=post_hook)
+        if use_head_logprobs(model, data):
+            # no logits: the head returns the log-probs (temperature 1)
+            seqlogp = model.module.forward(
+                data, n_mbs=n_mbs, post_hook=_sum_seq_logps, head_logprobs=1.0)
+        else:
+            seqlogp = model.module.forward(data, n_mbs=n_mbs, post_hook=post_hook)
         if seqlogp is None:  # pp mid stage
             return None
         # 2 sequences (pos, neg) per sample

@@ -30,7 +30,10 @@ from realhf_amd.interfaces import ppo_math
 from realhf_amd.models import moe as moe_mod
 from realhf_amd.models.generation import concat_prompt_to_generation_output
 from realhf_amd.ops import functional as ops
-from realhf_amd.parallel.tp import packed_shifted_logprobs
+from realhf_amd.parallel.tp import (
+    fused_head_logprob_enabled,
+    packed_shifted_logprobs,
+)
 from realhf_amd.runtime.engine import sample_to_packed
 from realhf_amd.utils.functional import (
     apply_logits_mask,
@@ -64,6 +67,21 @@ def _warp_logits_like_sampler(logits, cu, mb, temperature: float):
     apply_logits_mask(sub, lm.bool())       # in-place on the copy
     logits[rows] = sub
     return logits
+
+
+def use_head_logprobs(model: Model, data: SequenceSample) -> bool:
+    """Whether an inference call takes the fused head route
+    (REALHF_AMD_FUSED_HEAD_LOGPROB=1): the engine implements it, the model
+    has an LM head, and no recorded top-k/top-p mask has to be applied to
+    the logits (packed_logits_mask stays on the logits path)."""
+    engine = model.module
+    cfg = getattr(getattr(engine, "module", None), "config", None)
+    return (
+        fused_head_logprob_enabled()
+        and getattr(engine, "supports_head_logprobs", False)
+        and cfg is not None and not cfg.is_critic
+        and "packed_logits_mask" not in data.keys
+    )
 
 
 @torch.no_grad()
@@ -218,7 +236,12 @@ class PPOActorInterface(ModelInterface):
             _warp_logits_like_sampler(logits, cu, mb, self.gconfig.temperature)
             return packed_shifted_logprobs(logits, cu, ids)
 
-        logp = model.module.forward(data, n_mbs=n_mbs, post_hook=post_hook)
+        if use_head_logprobs(model, data):
+            # no logits: the head returns the log-probs themselves
+            logp = model.module.forward(
+                data, n_mbs=n_mbs, head_logprobs=self.gconfig.temperature)
+        else:
+            logp = model.module.forward(data, n_mbs=n_mbs, post_hook=post_hook)
         if logp is None:  # pp mid stage
             return None
         return SequenceSample(

@@ -659,6 +659,30 @@ class OutputHead(nn.Module):
                 return self._cap(o)
         return self._cap(_linear(h, w))  # [total, vocab/tp] — vocab-parallel logits
 
+    def logprobs(self, x, labels, inv_temperature: float = 1.0):
+        """fp32 [total] log p(labels) under cap -> temperature, 0 where the
+        label is IGNORE_INDEX: forward's norm, SP gather and weight, then
+        ops.head_logprobs over this rank's vocab slice, which never forms
+        the logits where its kernel applies.  Inference only."""
+        from realhf_amd.parallel.tp import IGNORE_INDEX
+
+        cfg = self.cfg
+        assert not cfg.is_critic and not torch.is_grad_enabled()
+        h = _norm(cfg, x, self.p[f"{self.i}.ln_f.weight"], self.p.get(f"{self.i}.ln_f.bias"))
+        if constants.has_current() and constants.sequence_parallel():
+            h = mappings.gather_from_sp_region(h)
+        h = mappings.copy_to_tp_region(h)
+        w = self.tied_w if self.tied_w is not None else self.p.get(f"{self.i}.head.weight")
+        tp = constants.tp_world_size() if constants.has_current() else 1
+        return ops.head_logprobs(
+            h, w, labels,
+            inv_temperature=inv_temperature,
+            softcap=cfg.final_logit_softcap,
+            vocab_start=(constants.tp_rank() if tp > 1 else 0) * w.shape[0],
+            group=constants.tp_group() if tp > 1 else None,
+            ignore_index=IGNORE_INDEX,
+        )
+
     def _cap(self, logits):
         """Final logit soft-cap (gemma-2), cap * tanh(logits / cap) in the
         logits' dtype; elementwise, so vocab-parallel shards take it as is."""

@@ -235,10 +235,14 @@ class ReaLModel(nn.Module):
         kv_caches: Optional[List[torch.Tensor]] = None,  # [(k,v)] per local block
         cache_seqlens: Optional[torch.Tensor] = None,
         decode: bool = False,
+        logprob_labels: Optional[torch.Tensor] = None,
+        logprob_inv_temperature: float = 1.0,
     ):
         """Run this PP stage.  First stage consumes packed_input_ids, later
         stages consume hidden_states.  Returns hidden states (mid stages)
-        or logits/values (last stage)."""
+        or logits/values (last stage).  With logprob_labels [total] the last
+        stage returns fp32 [total] log-probs of those labels instead of
+        logits (OutputHead.logprobs; inference only)."""
         assert self._offloaded is False, "model is offloaded; reload first"
         cfg = self.config
         if decode:
@@ -269,7 +273,10 @@ class ReaLModel(nn.Module):
             if idx == 0:
                 x = layer(packed_input_ids, positions)
             elif idx == cfg.n_layers + 1:
-                x = layer(x)
+                if logprob_labels is not None:
+                    x = layer.logprobs(x, logprob_labels, logprob_inv_temperature)
+                else:
+                    x = layer(x)
             else:
                 kc = vc = None
                 if kv_caches is not None:

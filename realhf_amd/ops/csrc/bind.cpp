@@ -81,6 +81,11 @@ std::vector<torch::Tensor> vocab_logprob_fwd(torch::Tensor logits,
 torch::Tensor vocab_logprob_bwd(torch::Tensor logits, torch::Tensor labels,
                                 torch::Tensor lse, torch::Tensor grad_out,
                                 long vocab_start, long ignore_index);
+// the same statistics straight from the hidden states: head GEMM fused with
+// the online log-sum-exp, no logits (softcap 0 = off, nsplit 0 = heuristic)
+std::vector<torch::Tensor> head_logprob_fwd(
+    torch::Tensor h, torch::Tensor w, torch::Tensor labels, long vocab_start,
+    long ignore_index, double inv_temperature, double softcap, long nsplit);
 // FP8 weight-only decode: per-row e4m3 quantizer (q one byte per element,
 // scale fp32 [N]) and the skinny GEMM that streams q instead of bf16 W
 std::vector<torch::Tensor> quantize_rows_e4m3(torch::Tensor w);
@@ -211,6 +216,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mcmc_search", &mcmc_search);
   m.def("vocab_logprob_fwd", &vocab_logprob_fwd);
   m.def("vocab_logprob_bwd", &vocab_logprob_bwd);
+  m.def("head_logprob_fwd", &head_logprob_fwd);
   m.def("quantize_rows_e4m3", &quantize_rows_e4m3);
   m.def("quantize_rows_e4m3_", &quantize_rows_e4m3_);
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);

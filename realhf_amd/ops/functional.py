@@ -26,6 +26,12 @@ HIP kernels (realhf_amd/ops/csrc/, reference op inventory SURVEY.md §2.2):
   fused_adamw        — flat-buffer AdamW (reference: apex fused adam via Megatron)
   vocab_logprobs     — per-token log-prob over a vocab slice, fwd/bwd without
                        fp32 [tokens, vocab] temporaries (opt-in, see parallel/tp.py)
+  head_logprobs      — the same log-probs from the last hidden states and the
+                       head weight, logits never formed: one MFMA GEMM whose
+                       epilogue is the online log-sum-exp (inference only,
+                       opt-in REALHF_AMD_FUSED_HEAD_LOGPROB=1);
+                       head_logprob_supported is its gate, head_logprobs_ref
+                       the oracle
   quantize_rows_e4m3 — per-row OCP e4m3 weight quantizer (q, scale) for FP8
                        weight-only decode; maybe_skinny_linear /
                        skinny_linear_nc take the pair as fp8=(q, scale) and
@@ -800,6 +806,70 @@ def vocab_logprobs(logits, labels, *, vocab_start=0, group=None,
     [n] log-sum-exp for backward."""
     return _VocabLogProbFn.apply(logits, labels.long(), int(vocab_start), group,
                                  int(ignore_index))
+
+
+# ---------------------------------------------------------------------------
+# Head log-probs: the same statistics straight from the hidden states
+# ---------------------------------------------------------------------------
+def _warp_head_logits(logits, inv_temperature, softcap):
+    if softcap:
+        logits = torch.tanh(logits / softcap) * softcap
+    return logits * inv_temperature if inv_temperature != 1.0 else logits
+
+
+def head_logprobs_ref(h, w, labels, *, inv_temperature=1.0, softcap=None,
+                      vocab_start=0, ignore_index=-100):
+    """(target, rowmax, sumexp) of vocab_logprob_stats_ref over the warped
+    logits x = softcap * tanh(h @ w^T / softcap) * inv_temperature, computed
+    in the dtype of h and w (fp64 in tests)."""
+    x = _warp_head_logits(h @ w.t(), inv_temperature, softcap)
+    v_local = x.shape[-1]
+    rowmax = x.max(dim=-1).values
+    sumexp = (x - rowmax.unsqueeze(-1)).exp().sum(dim=-1)
+    local = labels - vocab_start
+    in_range = (local >= 0) & (local < v_local)
+    target = x.gather(-1, local.clamp(0, v_local - 1).unsqueeze(-1)).squeeze(-1)
+    ign = labels == ignore_index
+    target = target.masked_fill(~in_range | ign, 0.0)
+    return target, rowmax.masked_fill(ign, 0.0), sumexp.masked_fill(ign, 1.0)
+
+
+def head_logprob_supported(h: torch.Tensor, w: torch.Tensor) -> bool:
+    """The one gate of the fused head kernel (head_logprob.hip): a HIP
+    device, bf16, H a multiple of 8, 16-byte aligned rows, grad mode off
+    (the kernel has no backward)."""
+    return (
+        not torch.is_grad_enabled()
+        and h.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+        and h.dim() == 2 and w.dim() == 2 and h.shape[1] == w.shape[1]
+        and h.shape[1] % 8 == 0 and h.shape[1] <= 1 << 22
+        and w.stride(1) == 1 and w.stride(0) % 8 == 0
+        and h.shape[1] <= w.stride(0) <= 1 << 22
+        and w.data_ptr() % 16 == 0
+        and w.is_cuda and _ops.use_hip(h)
+    )
+
+
+def head_logprobs(h, w, labels, *, inv_temperature=1.0, softcap=None,
+                  vocab_start=0, group=None, ignore_index=-100):
+    """fp32 log p(label) per row of the hidden states h [n, H] under the
+    head weight slice w [v_local, H] whose rows start at vocab_start: cap,
+    then temperature, as the sampler applies them.  Rows labelled
+    ignore_index give 0.  When head_logprob_supported the logits are never
+    formed (one fused GEMM + log-sum-exp kernel, fp32 throughout);
+    otherwise they are, in the dtype of h, and go through vocab_logprobs."""
+    labels = labels.long()
+    if not head_logprob_supported(h, w):
+        logits = _warp_head_logits(torch.nn.functional.linear(h, w),
+                                   inv_temperature, softcap)
+        return vocab_logprobs(logits, labels, vocab_start=vocab_start,
+                              group=group, ignore_index=ignore_index)
+    C = _ops.require_hip()
+    stats = C.head_logprob_fwd(h.contiguous(), w, labels.contiguous(),
+                               int(vocab_start), int(ignore_index),
+                               float(inv_temperature), float(softcap or 0.0), 0)
+    logp, _ = combine_vocab_stats(*stats, group=group)
+    return logp.masked_fill(labels == ignore_index, 0.0)
 
 
 # ---------------------------------------------------------------------------

@@ -11,6 +11,11 @@ logits through ops.functional.vocab_logprobs instead: the same three
 all-reduces, but the per-rank statistics come from one HIP pass over the
 logits and backward recomputes the softmax from the saved logits, so no
 fp32 [tokens, v_local] tensor exists inside a rank either.
+
+REALHF_AMD_FUSED_HEAD_LOGPROB=1 (opt-in, read at call time) goes one step
+further for inference calls: the model is asked for log-probs, and
+OutputHead.logprobs computes the statistics from the hidden states and the
+head weight (ops.functional.head_logprobs), so no logits exist at all.
 """
 import os
 
@@ -88,6 +93,31 @@ def vocab_parallel_logprobs(logits: torch.Tensor, labels: torch.Tensor):
     return _VocabParallelLogProbs.apply(logits, labels)
 
 
+def packed_next_token_labels(cu_seqlens: torch.Tensor,
+                             packed_input_ids: torch.Tensor):
+    """(labels [total], leave [total - bs]): every row labelled with its next
+    token, the last token of each sequence with IGNORE_INDEX; leave indexes
+    the predicting rows."""
+    from realhf_amd.utils.functional import (
+        build_leave_one_indices,
+        build_shift_one_indices,
+    )
+
+    total = packed_input_ids.shape[0]
+    leave = build_leave_one_indices(total, cu_seqlens)
+    shift = build_shift_one_indices(total, cu_seqlens)
+    labels = packed_input_ids.new_full((total,), IGNORE_INDEX)
+    labels[leave] = packed_input_ids[shift]
+    return labels, leave
+
+
+def fused_head_logprob_enabled() -> bool:
+    """REALHF_AMD_FUSED_HEAD_LOGPROB=1 (opt-in, read at call time): inference
+    calls that only need per-token log-probs ask the model for them
+    (OutputHead.logprobs) instead of logits."""
+    return os.environ.get("REALHF_AMD_FUSED_HEAD_LOGPROB") == "1"
+
+
 def packed_shifted_logprobs(
     logits: torch.Tensor, cu_seqlens: torch.Tensor, packed_input_ids: torch.Tensor
 ):
@@ -98,13 +128,12 @@ def packed_shifted_logprobs(
         build_shift_one_indices,
     )
 
-    total = packed_input_ids.shape[0]
-    leave = build_leave_one_indices(total, cu_seqlens)
-    shift = build_shift_one_indices(total, cu_seqlens)
     if _use_fused(logits):
         # no logits[leave] copy: every row runs, the last token of each
         # sequence is labelled ignore_index (logits not read, zero gradient)
-        labels = packed_input_ids.new_full((total,), IGNORE_INDEX)
-        labels[leave] = packed_input_ids[shift]
+        labels, leave = packed_next_token_labels(cu_seqlens, packed_input_ids)
         return vocab_parallel_logprobs(logits, labels)[leave]
+    total = packed_input_ids.shape[0]
+    leave = build_leave_one_indices(total, cu_seqlens)
+    shift = build_shift_one_indices(total, cu_seqlens)
     return vocab_parallel_logprobs(logits[leave], packed_input_ids[shift])

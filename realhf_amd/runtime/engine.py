@@ -26,6 +26,7 @@ from realhf_amd.base import constants, logging, seeding
 from realhf_amd.models import generation as genmod
 from realhf_amd.models import moe as moe_mod
 from realhf_amd.parallel.ddp import OptimizerConfig, ZeRO1Optimizer
+from realhf_amd.parallel.tp import packed_next_token_labels
 
 logger = logging.getLogger("engine")
 
@@ -108,17 +109,33 @@ class PipelinableTrainEngine(PipelinableEngine):
                 stats[k] = stats.get(k, 0.0) + float(v) / len(mbs)
         return stats
 
+    # forward(head_logprobs=...) is implemented here; interfaces check this
+    # attribute before they pass the keyword
+    supports_head_logprobs = True
+
     @torch.no_grad()
     def forward(self, input_: SequenceSample, n_mbs: Optional[int] = None,
                 post_hook: Optional[Callable] = None,
-                aggregate_fn: Callable = _default_aggregate):
+                aggregate_fn: Callable = _default_aggregate,
+                head_logprobs: Optional[float] = None):
+        """head_logprobs = a sampling temperature: the model is asked for
+        next-token log-probs under it instead of logits, and post_hook gets
+        the fp32 [total - bs] log-probs of the predicting rows."""
         self.model.eval()
         self._finish_ag()
         mbs = input_.split(n_mbs) if n_mbs and n_mbs > 1 and input_.bs >= n_mbs else [input_]
         outs = []
         for mb in mbs:
             ids, cu, mx = sample_to_packed(mb)
-            out = self.model(packed_input_ids=ids, cu_seqlens=cu, max_seqlen=mx)
+            if head_logprobs is not None:
+                labels, leave = packed_next_token_labels(cu, ids)
+                out = self.model(
+                    packed_input_ids=ids, cu_seqlens=cu, max_seqlen=mx,
+                    logprob_labels=labels,
+                    logprob_inv_temperature=1.0 / max(head_logprobs, 1e-5),
+                )[leave]
+            else:
+                out = self.model(packed_input_ids=ids, cu_seqlens=cu, max_seqlen=mx)
             if post_hook is not None:
                 out = post_hook(out, mb)
             outs.append(out)
